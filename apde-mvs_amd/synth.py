@@ -146,6 +146,7 @@ class _Quad:
 
 
 TEXTURES = ("smooth", "rich")
+RENDER_STRIP = 32  # rows rendered at a time
 
 
 def make_scene(width=160, height=120, num_src=4, seed=20251114, weak_patches=True, depth=6.0,
@@ -214,10 +215,19 @@ def make_scene(width=160, height=120, num_src=4, seed=20251114, weak_patches=Tru
     Kinv = np.linalg.inv(K)
 
     def render(cam, noise):
+        # in strips of rows: every operation below is per pixel, so the image is the same, and a
+        # strip's temporaries stay in cache (whole 6048x4032 float64 temporaries made the render
+        # memory-bound)
+        strips = [render_rows(cam, noise[y0:y0 + RENDER_STRIP], ys[y0:y0 + RENDER_STRIP])
+                  for y0 in range(0, height, RENDER_STRIP)]
+        return tuple(np.concatenate(part) for part in zip(*strips))
+
+    def render_rows(cam, noise, ys):
+        rows = len(ys)
         M = cam.R.T @ Kinv  # world-frame ray of pixel (x, y) with camera-frame z = 1
         C = cam.center
-        best_t = np.full((height, width), np.inf)
-        best_q = np.full((height, width), -1, np.int64)
+        best_t = np.full((rows, width), np.inf)
+        best_q = np.full((rows, width), -1, np.int64)
         hits = []
         for qi, q in enumerate(quads):
             t, s, r = q.intersect(C, M, xs, ys)
@@ -225,8 +235,8 @@ def make_scene(width=160, height=120, num_src=4, seed=20251114, weak_patches=Tru
             best_t = np.where(closer, t, best_t)
             best_q = np.where(closer, qi, best_q)
             hits.append((s, r))
-        val = np.zeros((height, width))
-        flat = np.zeros((height, width), bool)
+        val = np.zeros((rows, width))
+        flat = np.zeros((rows, width), bool)
         for qi, q in enumerate(quads):
             m = best_q == qi
             if m.any():

@@ -33,6 +33,12 @@ produced over RCCL (xGMI), and `value` at N > 1 pays the exchange; `exchange_ms`
 separately timed all-gathers (barrier, then the collective alone) and `rank_ms_per_step` the ranks'
 own per-step times (the value uses the max over ranks).
 
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) sets up, warms up, times the K steps and prints
+the line: the headline, and the roofline read from the timed steps' own HIP events and counters.
+`--dump-outputs DIR` also writes what the last timed step left (dump_outputs). Everything below that
+takes runs of its own (cpu_baseline, end_to_end and roofline_depth_to_weak, c2_first_init,
+rich_texture, sa_pass) is measured only with `--full` and is null in a plain run's line.
+
 Besides the headline the JSON line carries:
   roofline      the dominant kernels of the step, the Weak sweep (the anchor candidates -- k_gp_cost +
                 k_weak_cand_g + k_weak_cand_comb -- + 2 x k_sweep_weak_vm,
@@ -133,7 +139,9 @@ def fetch_calibration():
 
 def make_scene(W, H, N, world, texture, texture_scale=1.0):
     import synth
-    return synth.make_scene(W, H, max(N, world), seed=20251114, texture=texture, texture_scale=texture_scale)
+    # one render thread per view where the cores allow (the scene does not depend on their number)
+    return synth.make_scene(W, H, max(N, world), seed=20251114, texture=texture, texture_scale=texture_scale,
+                            workers=min(16, os.cpu_count() or 1))
 
 
 def first_init_priors(eng, sc, ids, N):
@@ -225,6 +233,32 @@ def timed_fresh_iterations(eng, arr, steps, warmup, barrier, exchange=None, exch
         barrier()
         done += n
     return elapsed + pairs_ms * 1e-3, step_ms, pairs_ms
+
+
+DUMP_PIXELS = 1 << 20  # 32 B per sampled pixel over the dumped arrays: 32 MiB
+
+
+def dump_outputs(eng, W, H, folder):
+    """What the timed path (apd_stage_iteration) left after its last step, as a caller reads it back
+    with apd_get_results: planes (n, 4: world normal + depth, f32) and selected_views (n, the
+    per-pixel view bit mask, f64) at the n pixels listed in pixels.npy (row-major indices, f64):
+    every pixel, or DUMP_PIXELS seeded draws from a larger image. The matching costs stay out: at C3
+    2 % of them are NaN, which a comparison by difference trips on. Scene, priors and the pass's
+    random numbers are seeded, so two builds run with the same arguments compare array for array."""
+    import apd_abi as A
+    planes = np.empty((H * W, 4), np.float32)
+    sel = np.empty(H * W, np.uint32)
+    s = A.ApdOutputs()
+    s.planes = A._ptr(planes, A.C.c_float)
+    s.selected_views = A._ptr(sel, A.C.c_uint32)
+    eng._check(eng.lib.apd_get_results(eng.ctx, A.C.byref(s)), "apd_get_results")
+    px = np.arange(H * W)
+    if px.size > DUMP_PIXELS:
+        px = np.sort(np.random.default_rng(20251114).integers(0, H * W, DUMP_PIXELS))
+    os.makedirs(folder, exist_ok=True)
+    for name, a in (("pixels", px.astype(np.float64)), ("planes", planes[px]),
+                    ("selected_views", sel[px].astype(np.float64))):
+        np.save(os.path.join(folder, name + ".npy"), a)
 
 
 def kernel_stats(eng, kind):
@@ -500,6 +534,12 @@ def main():
     ap.add_argument("--height", type=int, default=4032)
     ap.add_argument("--n-src", type=int, default=10)
     ap.add_argument("--texture", default="smooth", choices=["smooth", "rich"])
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one left (dump_outputs) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also measure everything else the line carries: end to end, the SA and "
+                         "texture-rich passes, C2 FIRST_INIT and the CPU baselines (each switched by its own "
+                         "option below); a plain run measures the headline only and reports those as null")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-threads", type=int, default=int(os.environ.get("OMP_NUM_THREADS", "16") or 16))
     ap.add_argument("--end-to-end", type=int, default=1, help="also time one full RunPatchMatch (0/1)")
@@ -539,23 +579,29 @@ def main():
             if torch.cuda.is_available():
                 torch.cuda.synchronize()
 
-    import apd_abi as A
-
     W, H, N = args.width, args.height, args.n_src
-    t0 = time.time()
-    sc = make_scene(W, H, N, world, args.texture)
-    t_scene = time.time() - t0
+
+    def timed_scene():
+        t0 = time.time()
+        scene = make_scene(W, H, N, world, args.texture)
+        return scene, time.time() - t0
+
+    # the scene renders on host threads while this one loads the library and opens the device
+    from concurrent.futures import ThreadPoolExecutor
+    with ThreadPoolExecutor(1) as pool:
+        scene_job = pool.submit(timed_scene)
+        import apd_abi as A
+        lib = A.load_library()
+        device = local_rank % max(1, lib.apd_device_count())
+        if dist and dist[2] != "nccl":
+            import torch
+            if torch.cuda.is_available():
+                torch.cuda.set_device(device)
+        eng = A.Engine(device, lib)
+        sc, t_scene = scene_job.result()
     n_views = len(sc.images)
     ref = rank % n_views
     ids = [ref] + [j for j, _ in sc.pairs[ref]][:N]
-
-    lib = A.load_library()
-    device = local_rank % max(1, lib.apd_device_count())
-    if dist and dist[2] != "nccl":
-        import torch
-        if torch.cuda.is_available():
-            torch.cuda.set_device(device)
-    eng = A.Engine(device, lib)
     t0 = time.time()
     priors = first_init_priors(eng, sc, ids, N)
     t_priors = time.time() - t0
@@ -582,6 +628,8 @@ def main():
     roof = weak_roofline(eng, args.steps, W, N)
     roof_strong_apd = strong_roofline(eng, W, N)
     eng.profile_reset(False)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(eng, W, H, args.dump_outputs)
     exch = None
     if dist:
         torch, tdist, backend = dist
@@ -619,14 +667,14 @@ def main():
 
     line = None
     if rank == 0:
-        e2e = end_to_end(eng, arr, sc, ref, W, H, N) if args.end_to_end else None
+        e2e = end_to_end(eng, arr, sc, ref, W, H, N) if (args.full and args.end_to_end) else None
         del arr
+        single = args.full and n_gpus == 1  # the secondary workloads: --full on one GPU
         sa_pass = None
-        if args.sa and n_gpus == 1:
+        if args.sa and single:
             sa_pass = apd_pass_once(eng, sc, ref, N, f"C5's per-GPU workload: the {workload_name(W, H, N, True)} pass "
                                                    f"with SAM-style segment labels as the SA mask (APD.cu:464-530)", sa=True)
         del sc
-        single = n_gpus == 1
         c2 = c2_first_init(eng, 6, 2) if (args.c2 and single) else None
         rich = None
         if args.rich and single and args.texture != "rich":

@@ -12,8 +12,9 @@ if [ "$WHAT" = tests ] || [ "$WHAT" = all ]; then
   timeout -k 10 300 python3 -u -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smoke.log" 2>&1
 fi
 if [ "$WHAT" = bench ] || [ "$WHAT" = all ]; then
-  timeout -k 10 600 python3 -u bench.py > "$OUT/bench.json" 2> "$OUT/bench.err"
+  timeout -k 10 600 python3 -u bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err"
+  R=$PWD
   cd /tmp
-  timeout -k 10 600 rocprofv3 --kernel-trace --stats -d "$GRAFT_REPO_ROOT/$OUT/prof" -o run --output-format csv -- python3 "$GRAFT_REPO_ROOT/bench.py" --no-cpu-baseline --end-to-end 0 --c2 0 --rich 0 --steps 6 --warmup 1 > "$GRAFT_REPO_ROOT/$OUT/prof_bench.json" 2> "$GRAFT_REPO_ROOT/$OUT/prof_bench.err"
+  timeout -k 10 600 rocprofv3 --kernel-trace --stats -d "$R/$OUT/prof" -o run --output-format csv -- python3 "$R/bench.py" --full --no-cpu-baseline --end-to-end 0 --c2 0 --rich 0 --steps 6 --warmup 1 > "$R/$OUT/prof_bench.json" 2> "$R/$OUT/prof_bench.err"
 fi
 echo ok

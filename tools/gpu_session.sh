@@ -19,12 +19,13 @@ for step in "$@"; do
     smoke) timeout -k 10 300 python3 -u -c "import __graft_entry__ as g; g.smoke()" > "$OUT/s$n.smoke.log" 2>&1 ;;
     ab) env_=${rest%%:*}; libs=${rest#*:}
         env $env_ timeout -k 10 600 python3 -u tools/ab_apd.py ${libs//,/ } > "$OUT/s$n.ab.log" 2>&1 ;;
-    bench) timeout -k 10 900 python3 -u bench.py $rest > "$OUT/s$n.bench.json" 2> "$OUT/s$n.bench.err" ;;
+    bench) timeout -k 10 900 python3 -u bench.py --full $rest > "$OUT/s$n.bench.json" 2> "$OUT/s$n.bench.err" ;;
     pmc) re=${rest%%:*}; r2=${rest#*:}; last=${r2%%:*}; bargs=${r2#*:}
          bash tools/pmc_c3.sh "$OUT/s$n.pmc" "$re" $bargs > "$OUT/s$n.pmc.log" 2>&1 ;;
-    prof) cd /tmp
-          timeout -k 10 700 rocprofv3 --kernel-trace --stats -d "$GRAFT_REPO_ROOT/$OUT/s$n.prof" -o run --output-format csv -- python3 "$GRAFT_REPO_ROOT/bench.py" --no-cpu-baseline --c2 0 --rich 0 --sa 0 --steps 6 --warmup 1 $rest > "$GRAFT_REPO_ROOT/$OUT/s$n.prof_bench.json" 2> "$GRAFT_REPO_ROOT/$OUT/s$n.prof_bench.err"
-          cd "$GRAFT_REPO_ROOT" ;;
+    prof) R=$PWD
+          cd /tmp
+          timeout -k 10 700 rocprofv3 --kernel-trace --stats -d "$R/$OUT/s$n.prof" -o run --output-format csv -- python3 "$R/bench.py" --full --no-cpu-baseline --c2 0 --rich 0 --sa 0 --steps 6 --warmup 1 $rest > "$R/$OUT/s$n.prof_bench.json" 2> "$R/$OUT/s$n.prof_bench.err"
+          cd "$R" ;;
     script) timeout -k 10 1100 bash ${rest%%,*} "$OUT/s$n.script" ${rest#*,} > "$OUT/s$n.script.log" 2>&1 ;;
     *) echo "unknown step $step"; exit 2 ;;
   esac

@@ -8,7 +8,7 @@ OUT=${1:-gpurun_out/pmc}
 RE=${2:-k_sweep_strong}
 mkdir -p "$OUT"
 export TMPDIR=/tmp
-CMD="python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --end-to-end 0"
+CMD="python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --end-to-end 0"
 i=0
 for grp in \
   "SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CU_CYCLES SQ_INSTS_VALU SQ_INSTS_VMEM_RD SQ_INSTS_LDS SQ_INSTS_SALU SQ_ACTIVE_INST_VALU" \
