@@ -229,6 +229,10 @@ EXPORTS = ["apd_abi_version", "apd_device_count", "apd_create", "apd_destroy", "
            "apd_fusion_last_error", "apd_fusion_set_views", "apd_fusion_weak_filter", "apd_fusion_consistency",
            "apd_fusion_tat_levels"]
 
+# include/apd_eval.h: its own list (EXPORTS is the apd_hip.h + apd_fusion.h set apd_abi_version() covers)
+EVAL_EXPORTS = ["apd_eval_create", "apd_eval_destroy", "apd_eval_last_error", "apd_eval_set_target",
+                "apd_eval_distances", "apd_eval_voxel_downsample", "apd_eval_get_timing"]
+
 
 class ApdFusionView(C.Structure):  # include/apd_fusion.h
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("camera", ApdCamera),
@@ -316,6 +320,22 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     lib.apd_epilogue.restype = C.c_int32
     lib.apd_epilogue.argtypes = [C.c_int32, C.c_int32, C.POINTER(C.c_float), C.c_float, C.c_float,
                                  C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_uint8)]
+    # include/apd_eval.h
+    lib.apd_eval_create.restype = C.c_void_p
+    lib.apd_eval_create.argtypes = [C.c_int32]
+    lib.apd_eval_destroy.argtypes = [C.c_void_p]
+    lib.apd_eval_last_error.restype = C.c_char_p
+    lib.apd_eval_last_error.argtypes = [C.c_void_p]
+    lib.apd_eval_set_target.restype = C.c_int32
+    lib.apd_eval_set_target.argtypes = [C.c_void_p, C.c_int64, C.c_void_p]
+    lib.apd_eval_distances.restype = C.c_int32
+    lib.apd_eval_distances.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_float, C.c_void_p, C.c_int32,
+                                       C.c_void_p, C.c_void_p]
+    lib.apd_eval_voxel_downsample.restype = C.c_int32
+    lib.apd_eval_voxel_downsample.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]
+    lib.apd_eval_get_timing.restype = C.c_int32
+    lib.apd_eval_get_timing.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                        C.POINTER(C.c_double)]
     return lib
 
 
@@ -378,6 +398,151 @@ class FusionEngine:
             self.close()
         except Exception:
             pass
+
+
+class EvalEngine:
+    """One apd_eval_ctx (include/apd_eval.h): truncated nearest-neighbour distances to a target cloud
+    and voxel down-sampling. Clouds are (n, 3) float32: numpy arrays (results come back as numpy) or
+    torch tensors on the context's device (results come back as tensors there; torch's current
+    stream is waited for first, as for every device input of this library)."""
+
+    def __init__(self, device: int = 0, lib: Optional[C.CDLL] = None):
+        self.lib = lib or load_library()
+        self.device = device
+        self.ctx = self.lib.apd_eval_create(device)
+        if not self.ctx:
+            raise ApdError("apd_eval_create failed: " + (self.lib.apd_eval_last_error(None) or b"?").decode())
+
+    def _check(self, st: int, what: str):
+        if st != 0:
+            msg = (self.lib.apd_eval_last_error(self.ctx) or b"").decode()
+            raise ApdError(f"{what} -> {STATUS.get(st, st)}: {msg}")
+
+    @staticmethod
+    def _cloud(xyz):
+        """(buffer kept alive, n, address or None, is_device)"""
+        a = _keep(xyz, np.float32)
+        if tuple(a.shape[1:]) != (3,) or len(a.shape) != 2:
+            raise ValueError(f"a cloud is (n, 3) float32, got shape {tuple(a.shape)}")
+        dev = hasattr(a, "data_ptr")
+        n = int(a.shape[0])
+        addr = (a.data_ptr() if dev else a.ctypes.data) if n else None
+        return a, n, addr, dev
+
+    def set_target_ptr(self, n: int, xyz_ptr):
+        self._check(self.lib.apd_eval_set_target(self.ctx, n, xyz_ptr), "apd_eval_set_target")
+
+    def set_target(self, xyz):
+        a, n, addr, _ = self._cloud(xyz)
+        _torch_device_sync(a)
+        self.set_target_ptr(n, addr)
+
+    def distances_ptr(self, n: int, xyz_ptr, max_dist: float, dist_ptr, num_tol: int = 0, tol_ptr=None,
+                      within_ptr=None):
+        self._check(self.lib.apd_eval_distances(self.ctx, n, xyz_ptr, max_dist, dist_ptr, num_tol, tol_ptr,
+                                                within_ptr), "apd_eval_distances")
+
+    def distances(self, xyz, max_dist: float, tolerances=None, want_dist: bool = True):
+        """(dist float32[n] or None, within int64[k] or None)"""
+        a, n, addr, dev = self._cloud(xyz)
+        tol = None if tolerances is None else np.ascontiguousarray(tolerances, np.float32).reshape(-1)
+        k = 0 if tol is None else len(tol)
+        if dev:
+            import torch
+            dist = torch.empty(n, dtype=torch.float32, device=a.device) if want_dist else None
+            within = torch.zeros(k, dtype=torch.int64, device=a.device) if tol is not None else None
+            _torch_device_sync(a, dist, within)
+            dptr = dist.data_ptr() if (dist is not None and n) else None
+            wptr = within.data_ptr() if (within is not None and k) else None
+        else:
+            dist = np.empty(n, np.float32) if want_dist else None
+            within = np.zeros(k, np.int64) if tol is not None else None
+            dptr = dist.ctypes.data if (dist is not None and n) else None
+            wptr = within.ctypes.data if (within is not None and k) else None
+        self.distances_ptr(n, addr, max_dist, dptr, k, tol.ctypes.data if k else None, wptr)
+        return dist, within
+
+    def voxel_downsample_ptr(self, n: int, xyz_ptr, voxel: float, keep_ptr) -> int:
+        n_keep = C.c_int64(0)
+        self._check(self.lib.apd_eval_voxel_downsample(self.ctx, n, xyz_ptr, voxel, keep_ptr,
+                                                       C.addressof(n_keep)), "apd_eval_voxel_downsample")
+        return n_keep.value
+
+    def voxel_downsample(self, xyz, voxel: float):
+        """Ascending int32 indices of the lowest-index point of every occupied voxel."""
+        a, n, addr, dev = self._cloud(xyz)
+        if dev:
+            import torch
+            keep = torch.empty(max(n, 1), dtype=torch.int32, device=a.device)
+            _torch_device_sync(a, keep)
+            kptr = keep.data_ptr()
+        else:
+            keep = np.empty(max(n, 1), np.int32)
+            kptr = keep.ctypes.data
+        return keep[:self.voxel_downsample_ptr(n, addr, voxel, kptr)]
+
+    def timing(self) -> dict:
+        b, q, v = C.c_double(), C.c_double(), C.c_double()
+        self._check(self.lib.apd_eval_get_timing(self.ctx, C.byref(b), C.byref(q), C.byref(v)), "apd_eval_get_timing")
+        return {"build_ms": b.value, "query_ms": q.value, "voxel_ms": v.value}
+
+    def close(self):
+        if self.ctx:
+            self.lib.apd_eval_destroy(self.ctx)
+            self.ctx = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+ETH3D_TOLERANCES = (0.01, 0.02, 0.05, 0.1, 0.2, 0.5)  # the ones tools/eval_eth_train.py passes
+
+
+def cloud_metrics(rec_xyz, gt_xyz, tolerances=ETH3D_TOLERANCES, max_dist=None, voxel: float = 0.0,
+                  engine: Optional[EvalEngine] = None) -> dict:
+    """Accuracy / completeness / F1 of a reconstructed cloud against a ground-truth cloud (numpy
+    (n, 3) float32), the definitions the `apd_eval` command line shares: R and G are the clouds after
+    dropping non-finite points and, for voxel > 0, down-sampling each on its own; accuracy =
+    #{dist(R_i, G) <= t} / |R|, completeness = #{dist(G_j, R) <= t} / |G|, F1 = 2ac / (a + c), each
+    ratio 0 when its denominator is 0. Plain nearest-neighbour distances truncated at max_dist
+    (default: the largest tolerance); no free-space or visibility modelling."""
+    tol = np.ascontiguousarray(tolerances, np.float32).reshape(-1)
+    md = float(tol.max()) if max_dist is None else float(np.float32(max_dist))
+    eng = engine or EvalEngine()
+    out = {"tolerances": [float(t) for t in tol], "max_dist": md, "voxel": float(np.float32(voxel)), "timing_ms": {}}
+    try:
+        clouds = {}
+        for name, xyz in (("rec", rec_xyz), ("gt", gt_xyz)):
+            a = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+            info = {"points_in": int(len(a))}
+            a = a[np.isfinite(a).all(axis=1)]
+            info["points_finite"] = int(len(a))
+            if voxel > 0:
+                a = np.ascontiguousarray(a[eng.voxel_downsample(a, voxel)])
+            info["points"] = int(len(a))
+            clouds[name] = a
+            out[name] = info
+        ratios = {}
+        for name, q, t in (("accuracy", "rec", "gt"), ("completeness", "gt", "rec")):
+            eng.set_target(clouds[t])
+            dist, within = eng.distances(clouds[q], md, tol)
+            tm = eng.timing()
+            fin = np.isfinite(dist)
+            nfin = int(fin.sum())
+            n = len(dist)
+            mean = float(np.cumsum(dist[fin].astype(np.float64))[-1] / nfin) if nfin else 0.0  # index order
+            ratios[name] = [int(w) / n if n else 0.0 for w in within]
+            out[name] = {"within": [int(w) for w in within], "inf": n - nfin, "mean": mean, "ratio": ratios[name]}
+            out["timing_ms"][name] = {"build_ms": tm["build_ms"], "query_ms": tm["query_ms"]}
+        out["f1"] = [2 * a * c / (a + c) if a + c > 0 else 0.0
+                     for a, c in zip(ratios["accuracy"], ratios["completeness"])]
+    finally:
+        if engine is None:
+            eng.close()
+    return out
 
 
 class Engine:

@@ -1,0 +1,714 @@
+// apd_eval.hip — device side of the point-cloud evaluation (include/apd_eval.h): truncated
+// nearest-neighbour distances between two clouds and voxel down-sampling.
+//
+// Search structure: a Morton-sorted implicit bounding-volume tree.
+//   - finite targets are quantised to 21 bits per axis over their bounding box (in double) and sorted
+//     by the 63-bit Morton key (rocPRIM radix sort, stable, so the order is the same every run);
+//   - leaves are runs of LEAF consecutive sorted points with their exact fp32 min/max box;
+//   - level l+1 holds the min/max of every FAN consecutive boxes of level l, up to a single root.
+//     Children are index arithmetic: node i of level l+1 covers nodes [i*FAN, i*FAN+FAN) of level l.
+//   - queries are sorted by the same key so that the lanes of a wave walk the same part of the tree;
+//     each lane first evaluates the leaf at its own position in the sorted target keys, which makes
+//     the bound tight before the descent from the root starts.
+// Compiled with -ffp-contract=off: the distance statement is the contract, bit for bit.
+#include <hip/hip_runtime.h>
+#include <rocprim/device/device_radix_sort.hpp>
+#include <rocprim/device/device_scan.hpp>
+
+#include <cmath>
+#include <cstdint>
+#include <cstring>
+#include <limits>
+#include <string>
+#include <vector>
+
+#include "../../include/apd_eval.h"
+
+namespace {
+
+constexpr int LEAF = 32;        // points per leaf
+constexpr int FAN = 8;          // children per internal node
+constexpr int MAX_LEVELS = 12;  // 32 * 8^9 > 2^31 points: at most 10 levels are ever used
+// deepest stack: popping an internal node pushes at most FAN children (net +7) once per level
+constexpr int STACK = 1 + (FAN - 1) * (MAX_LEVELS - 1);
+constexpr int BLOCK = 256;
+constexpr uint64_t KEY_NONE = ~0ull;  // non-finite point: sorts behind every 63-bit key
+constexpr int TOL_CHUNK = 8;
+
+struct Tree {
+    const float4 *pts;    // sorted finite targets, w unused
+    const float4 *boxes;  // per node: lo, hi
+    const uint64_t *keys; // sorted Morton keys of pts
+    int nf;               // finite targets
+    int levels;           // number of levels, level 0 = leaves, level levels-1 = root
+    int off[MAX_LEVELS];  // first node of each level in boxes (in nodes)
+    int cnt[MAX_LEVELS];
+};
+
+__device__ __forceinline__ uint32_t f2ord(float f) {
+    const uint32_t u = __float_as_uint(f);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float ord2f(uint32_t u) {
+    return __uint_as_float((u & 0x80000000u) ? (u & 0x7FFFFFFFu) : ~u);
+}
+__device__ __forceinline__ bool finite3(float x, float y, float z) {
+    return isfinite(x) && isfinite(y) && isfinite(z);
+}
+
+// bounds[0..2] = min, [3..5] = max of the finite points (order-preserving uint encoding; integer
+// atomics, so the result does not depend on the order of arrival)
+__global__ void __launch_bounds__(BLOCK) k_bounds(const float *__restrict__ xyz, int n, uint32_t *bounds) {
+    uint32_t lo[3] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu}, hi[3] = {0u, 0u, 0u};
+    for (int i = blockIdx.x * BLOCK + threadIdx.x; i < n; i += gridDim.x * BLOCK) {
+        const float x = xyz[3 * (size_t)i], y = xyz[3 * (size_t)i + 1], z = xyz[3 * (size_t)i + 2];
+        if (!finite3(x, y, z)) continue;
+        const uint32_t e[3] = {f2ord(x), f2ord(y), f2ord(z)};
+        for (int a = 0; a < 3; ++a) {
+            lo[a] = min(lo[a], e[a]);
+            hi[a] = max(hi[a], e[a]);
+        }
+    }
+    for (int a = 0; a < 3; ++a) {
+        for (int s = 32; s > 0; s >>= 1) {
+            lo[a] = min(lo[a], (uint32_t)__shfl_xor((int)lo[a], s));
+            hi[a] = max(hi[a], (uint32_t)__shfl_xor((int)hi[a], s));
+        }
+    }
+    if ((threadIdx.x & 63) == 0) {
+        for (int a = 0; a < 3; ++a) {
+            if (lo[a] != 0xFFFFFFFFu) atomicMin(&bounds[a], lo[a]);
+            if (hi[a] != 0u) atomicMax(&bounds[3 + a], hi[a]);
+        }
+    }
+}
+
+__device__ __forceinline__ uint64_t spread21(uint32_t v) {
+    uint64_t x = v & 0x1FFFFFu;
+    x = (x | x << 32) & 0x1F00000000FFFFull;
+    x = (x | x << 16) & 0x1F0000FF0000FFull;
+    x = (x | x << 8) & 0x100F00F00F00F00Full;
+    x = (x | x << 4) & 0x10C30C30C30C30C3ull;
+    x = (x | x << 2) & 0x1249249249249249ull;
+    return x;
+}
+
+// Morton key of a point over the target's bounding box, quantised in double; a zero extent maps the
+// axis to cell 0 and points outside the box (queries) are clamped to its faces.
+__device__ __forceinline__ uint32_t quant21(float v, uint32_t lo_e, uint32_t hi_e) {
+    const double lo = (double)ord2f(lo_e), ext = (double)ord2f(hi_e) - lo;
+    if (!(ext > 0.0)) return 0u;
+    double t = ((double)v - lo) * (2097152.0 / ext);
+    t = t < 0.0 ? 0.0 : (t > 2097151.0 ? 2097151.0 : t);
+    return (uint32_t)t;
+}
+
+__global__ void __launch_bounds__(BLOCK) k_morton_keys(const float *__restrict__ xyz, int n,
+                                                       const uint32_t *__restrict__ bounds, uint64_t *keys, int *idx,
+                                                       unsigned long long *n_finite) {
+    const int i = blockIdx.x * BLOCK + threadIdx.x;
+    bool fin = false;
+    if (i < n) {
+        const float x = xyz[3 * (size_t)i], y = xyz[3 * (size_t)i + 1], z = xyz[3 * (size_t)i + 2];
+        fin = finite3(x, y, z);
+        uint64_t k = KEY_NONE;
+        if (fin)
+            k = spread21(quant21(x, bounds[0], bounds[3])) << 2 | spread21(quant21(y, bounds[1], bounds[4])) << 1 |
+                spread21(quant21(z, bounds[2], bounds[5]));
+        keys[i] = k;
+        idx[i] = i;
+    }
+    if (n_finite) {  // one integer atomic per wave
+        const unsigned long long m = __ballot(fin);
+        if ((threadIdx.x & 63) == 0 && m) atomicAdd(n_finite, (unsigned long long)__popcll(m));
+    }
+}
+
+__global__ void __launch_bounds__(BLOCK) k_gather_points(const float *__restrict__ xyz, const int *__restrict__ idx,
+                                                         int nf, float4 *pts) {
+    const int i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= nf) return;
+    const size_t s = 3 * (size_t)idx[i];
+    pts[i] = make_float4(xyz[s], xyz[s + 1], xyz[s + 2], 0.0f);
+}
+
+__global__ void __launch_bounds__(BLOCK) k_leaf_boxes(const float4 *__restrict__ pts, int nf, int nleaf,
+                                                      float4 *boxes) {
+    const int l = blockIdx.x * BLOCK + threadIdx.x;
+    if (l >= nleaf) return;
+    const int b = l * LEAF, e = min(b + LEAF, nf);
+    float4 p = pts[b];
+    float lx = p.x, ly = p.y, lz = p.z, hx = p.x, hy = p.y, hz = p.z;
+    for (int j = b + 1; j < e; ++j) {
+        p = pts[j];
+        lx = fminf(lx, p.x); ly = fminf(ly, p.y); lz = fminf(lz, p.z);
+        hx = fmaxf(hx, p.x); hy = fmaxf(hy, p.y); hz = fmaxf(hz, p.z);
+    }
+    boxes[2 * (size_t)l] = make_float4(lx, ly, lz, 0.0f);
+    boxes[2 * (size_t)l + 1] = make_float4(hx, hy, hz, 0.0f);
+}
+
+__global__ void __launch_bounds__(BLOCK) k_upper_boxes(const float4 *__restrict__ child, int nchild, int nparent,
+                                                       float4 *parent) {
+    const int p = blockIdx.x * BLOCK + threadIdx.x;
+    if (p >= nparent) return;
+    const int b = p * FAN, e = min(b + FAN, nchild);
+    float4 lo = child[2 * (size_t)b], hi = child[2 * (size_t)b + 1];
+    for (int j = b + 1; j < e; ++j) {
+        const float4 l2 = child[2 * (size_t)j], h2 = child[2 * (size_t)j + 1];
+        lo.x = fminf(lo.x, l2.x); lo.y = fminf(lo.y, l2.y); lo.z = fminf(lo.z, l2.z);
+        hi.x = fmaxf(hi.x, h2.x); hi.y = fmaxf(hi.y, h2.y); hi.z = fmaxf(hi.z, h2.z);
+    }
+    parent[2 * (size_t)p] = lo;
+    parent[2 * (size_t)p + 1] = hi;
+}
+
+__device__ __forceinline__ float point_d2(float qx, float qy, float qz, const float4 t) {
+    const float dx = qx - t.x, dy = qy - t.y, dz = qz - t.z;
+    return (dx * dx + dy * dy) + dz * dz;
+}
+
+__device__ __forceinline__ float box_d2(float qx, float qy, float qz, const float4 lo, const float4 hi) {
+    const float gx = fmaxf(fmaxf(lo.x - qx, qx - hi.x), 0.0f);
+    const float gy = fmaxf(fmaxf(lo.y - qy, qy - hi.y), 0.0f);
+    const float gz = fmaxf(fmaxf(lo.z - qz, qz - hi.z), 0.0f);
+    return (gx * gx + gy * gy) + gz * gz;
+}
+
+__device__ __forceinline__ void eval_leaf(const Tree &T, int leaf, float qx, float qy, float qz, float &cur,
+                                          bool &found) {
+    const int b = leaf * LEAF, e = min(b + LEAF, T.nf);
+    for (int j = b; j < e; ++j) {
+        const float d2 = point_d2(qx, qy, qz, T.pts[j]);  // one 16-byte load per point
+        if (d2 <= cur) {
+            cur = d2;
+            found = true;
+        }
+    }
+}
+
+// One lane per query, queries in Morton order.
+//
+// Exactness of the pruning. For a box [lo, hi] and a point t inside it, per axis:
+//   q < lo:  lo - q <= t - q exactly, and fp32 subtraction is monotone, so fl(lo - q) <= fl(t - q)
+//            = |fl(q - t)|;   q > hi: likewise with q - hi;   otherwise g = 0 <= |dx|.
+// fp32 multiplication and addition of non-negative values are monotone too, and box_d2 uses the
+// same statement (gx*gx + gy*gy) + gz*gz as point_d2, so box_d2 <= the COMPUTED d2 of every point
+// in the box. A node is skipped iff box_d2 > cur (strict), where cur is the smallest computed d2 so
+// far: nothing that could lower (or tie) the minimum is lost, with no margin.
+// The cut-off applies to sqrtf(min d2), not to d2. The initial bound `bound_d2` is the LARGEST
+// float b with sqrtf(b) <= max_dist, found by the host by stepping floats (not a rounded
+// max_dist*max_dist): sqrtf is monotone, so every d2 whose root passes the cut-off is <= bound_d2
+// and survives the pruning, and everything above it would be cut anyway.
+//
+// The per-lane stack (STACK entries of node + box distance) is indexed at run time and therefore
+// lives in scratch memory.
+__global__ void __launch_bounds__(BLOCK) k_nearest(const Tree T, int nq, const uint64_t *__restrict__ qkeys,
+                                                   const int *__restrict__ qidx, const float *__restrict__ qxyz,
+                                                   float bound_d2, float max_dist, float *__restrict__ dist) {
+    const int i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= nq) return;
+    const int qi = qidx[i];
+    const uint64_t key = qkeys[i];
+    const float inf = __uint_as_float(0x7F800000u);
+    if (key == KEY_NONE || T.nf == 0) {
+        dist[qi] = inf;
+        return;
+    }
+    const float qx = qxyz[3 * (size_t)qi], qy = qxyz[3 * (size_t)qi + 1], qz = qxyz[3 * (size_t)qi + 2];
+    float cur = bound_d2;
+    bool found = false;
+
+    // the leaf at the query's own position in the sorted keys
+    int lo = 0, hi = T.nf;
+    while (lo < hi) {
+        const int mid = lo + ((hi - lo) >> 1);
+        if (T.keys[mid] < key) lo = mid + 1; else hi = mid;
+    }
+    const int leaf0 = min(lo, T.nf - 1) / LEAF;
+    eval_leaf(T, leaf0, qx, qy, qz, cur, found);
+
+    uint32_t st_node[STACK];  // level << 27 | index (at most 2^26 leaves)
+    float st_d2[STACK];
+    int sp = 0;
+    if (T.levels > 1) {
+        st_node[0] = (uint32_t)(T.levels - 1) << 27;
+        st_d2[0] = 0.0f;
+        sp = 1;
+    }
+    while (sp > 0) {
+        --sp;
+        if (st_d2[sp] > cur) continue;
+        const int lvl = (int)(st_node[sp] >> 27), idx = (int)(st_node[sp] & 0x7FFFFFFu);
+        const int cl = lvl - 1;
+        const int b = idx * FAN, e = min(b + FAN, T.cnt[cl]);
+        const float4 *cb = T.boxes + 2 * (size_t)T.off[cl];
+        for (int c = b; c < e; ++c) {
+            const float bd = box_d2(qx, qy, qz, cb[2 * (size_t)c], cb[2 * (size_t)c + 1]);
+            if (bd > cur) continue;
+            if (cl == 0) {
+                if (c != leaf0) eval_leaf(T, c, qx, qy, qz, cur, found);
+            } else if (sp < STACK) {  // always true (see STACK); keeps the store in bounds regardless
+                st_node[sp] = (uint32_t)cl << 27 | (uint32_t)c;
+                st_d2[sp] = bd;
+                ++sp;
+            }
+        }
+    }
+    float r = inf;
+    if (found) {
+        const float m = sqrtf(cur);
+        if (m <= max_dist) r = m;
+    }
+    dist[qi] = r;
+}
+
+// within[k] += #{dist <= tol[k]} for up to TOL_CHUNK tolerances: per-lane integer counts over a
+// grid-stride loop, a wave reduction, then one integer atomic per wave and tolerance.
+struct TolChunk {
+    float tol[TOL_CHUNK];
+    int n;
+};
+__global__ void __launch_bounds__(BLOCK) k_count_within(const float *__restrict__ dist, int n, TolChunk tc,
+                                                        unsigned long long *within) {
+    unsigned int c[TOL_CHUNK];
+    for (int k = 0; k < TOL_CHUNK; ++k) c[k] = 0;
+    for (int i = blockIdx.x * BLOCK + threadIdx.x; i < n; i += gridDim.x * BLOCK) {
+        const float d = dist[i];
+        for (int k = 0; k < TOL_CHUNK; ++k) c[k] += (k < tc.n && d <= tc.tol[k]) ? 1u : 0u;
+    }
+    for (int k = 0; k < TOL_CHUNK; ++k) {
+        if (k >= tc.n) break;
+        unsigned int v = c[k];
+        for (int s = 32; s > 0; s >>= 1) v += (unsigned int)__shfl_xor((int)v, s);
+        if ((threadIdx.x & 63) == 0 && v) atomicAdd(&within[k], (unsigned long long)v);
+    }
+}
+
+// ---- voxel down-sampling ------------------------------------------------------------------------
+
+// floorf(coordinate / voxel) per axis as a float (an exact integer, possibly huge) and its min/max
+__global__ void __launch_bounds__(BLOCK) k_voxel_bounds(const float *__restrict__ xyz, int n, float voxel,
+                                                        uint32_t *bounds) {
+    uint32_t lo[3] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu}, hi[3] = {0u, 0u, 0u};
+    for (int i = blockIdx.x * BLOCK + threadIdx.x; i < n; i += gridDim.x * BLOCK) {
+        const float x = xyz[3 * (size_t)i], y = xyz[3 * (size_t)i + 1], z = xyz[3 * (size_t)i + 2];
+        if (!finite3(x, y, z)) continue;
+        const uint32_t e[3] = {f2ord(floorf(x / voxel)), f2ord(floorf(y / voxel)), f2ord(floorf(z / voxel))};
+        for (int a = 0; a < 3; ++a) {
+            lo[a] = min(lo[a], e[a]);
+            hi[a] = max(hi[a], e[a]);
+        }
+    }
+    for (int a = 0; a < 3; ++a) {
+        for (int s = 32; s > 0; s >>= 1) {
+            lo[a] = min(lo[a], (uint32_t)__shfl_xor((int)lo[a], s));
+            hi[a] = max(hi[a], (uint32_t)__shfl_xor((int)hi[a], s));
+        }
+    }
+    if ((threadIdx.x & 63) == 0) {
+        for (int a = 0; a < 3; ++a) {
+            if (lo[a] != 0xFFFFFFFFu) atomicMin(&bounds[a], lo[a]);
+            if (hi[a] != 0u) atomicMax(&bounds[3 + a], hi[a]);
+        }
+    }
+}
+
+// key = (ix - min_x) << 42 | (iy - min_y) << 21 | (iz - min_z); the caller has checked that every
+// span is below 2^21, and the difference of two integer-valued floats that close is exact in double
+__global__ void __launch_bounds__(BLOCK) k_voxel_keys(const float *__restrict__ xyz, int n, float voxel, float mx,
+                                                      float my, float mz, uint64_t *keys, int *idx) {
+    const int i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const float x = xyz[3 * (size_t)i], y = xyz[3 * (size_t)i + 1], z = xyz[3 * (size_t)i + 2];
+    uint64_t k = KEY_NONE;
+    if (finite3(x, y, z)) {
+        const uint64_t ox = (uint64_t)((double)floorf(x / voxel) - (double)mx) & 0x1FFFFFull;
+        const uint64_t oy = (uint64_t)((double)floorf(y / voxel) - (double)my) & 0x1FFFFFull;
+        const uint64_t oz = (uint64_t)((double)floorf(z / voxel) - (double)mz) & 0x1FFFFFull;
+        k = ox << 42 | oy << 21 | oz;
+    }
+    keys[i] = k;
+    idx[i] = i;
+}
+
+// the sort is stable and the indices went in ascending, so the first entry of every run of equal
+// keys is the lowest input index of that voxel
+__global__ void __launch_bounds__(BLOCK) k_voxel_heads(const uint64_t *__restrict__ keys, const int *__restrict__ idx,
+                                                       int n, int *flag) {
+    const int i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const uint64_t k = keys[i];
+    if (k != KEY_NONE && (i == 0 || keys[i - 1] != k)) flag[idx[i]] = 1;
+}
+
+__global__ void __launch_bounds__(BLOCK) k_voxel_compact(const int *__restrict__ flag, const int *__restrict__ pos,
+                                                         int n, int *keep, unsigned long long *n_keep) {
+    const int i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= n) return;
+    if (flag[i]) keep[pos[i]] = i;
+    if (i == n - 1) *n_keep = (unsigned long long)(pos[i] + flag[i]);
+}
+
+struct Buf {
+    void *p = nullptr;
+    size_t bytes = 0;
+};
+
+inline int grid_for(int64_t n) { return (int)((n + BLOCK - 1) / BLOCK); }
+inline int grid_capped(int64_t n) { return (int)std::min<int64_t>((n + BLOCK - 1) / BLOCK, 4096); }
+
+}  // namespace
+
+struct apd_eval_ctx {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    std::string err;
+    // target
+    Buf t_xyz, t_keys, t_keys_s, t_idx, t_idx_s, t_pts, t_boxes;
+    // query / voxel working set
+    Buf q_xyz, q_keys, q_keys_s, q_idx, q_idx_s, q_dist, q_aux;
+    Buf sort_tmp, small;  // small: bounds (6 u32) at 0, counters (u64) from byte 64
+    Tree tree{};
+    bool has_target = false;
+    double build_ms = 0.0, query_ms = 0.0, voxel_ms = 0.0;
+};
+
+#define EV_OK(ctx, call)                                                                           \
+    do {                                                                                           \
+        hipError_t e_ = (call);                                                                    \
+        if (e_ != hipSuccess) {                                                                    \
+            (ctx)->err = std::string(#call) + ": " + hipGetErrorString(e_);                        \
+            return APD_EDEVICE;                                                                    \
+        }                                                                                          \
+    } while (0)
+
+static int grow(apd_eval_ctx *ctx, Buf &b, size_t bytes) {
+    if (b.bytes >= bytes && b.p) return APD_OK;
+    if (b.p) (void)hipFree(b.p);
+    b.p = nullptr;
+    b.bytes = 0;
+    if (bytes == 0) bytes = 16;
+    if (hipMalloc(&b.p, bytes) != hipSuccess) {
+        b.p = nullptr;
+        ctx->err = "apd_eval: device allocation of " + std::to_string(bytes) + " bytes failed";
+        return APD_ENOMEM;
+    }
+    b.bytes = bytes;
+    return APD_OK;
+}
+
+static int check_n(apd_eval_ctx *ctx, const char *what, int64_t n, const void *p) {
+    if (n < 0 || n > (int64_t)INT32_MAX) {
+        ctx->err = std::string(what) + ": point count out of range";
+        return APD_EINVAL;
+    }
+    if (n > 0 && !p) {
+        ctx->err = std::string(what) + ": NULL point array";
+        return APD_EINVAL;
+    }
+    return APD_OK;
+}
+
+// keys/idx -> keys_s/idx_s, stable, all 64 bits
+static int sort_pairs(apd_eval_ctx *ctx, Buf &keys, Buf &keys_s, Buf &idx, Buf &idx_s, int n) {
+    size_t tb = 0;
+    EV_OK(ctx, rocprim::radix_sort_pairs(nullptr, tb, (uint64_t *)keys.p, (uint64_t *)keys_s.p, (int *)idx.p,
+                                         (int *)idx_s.p, (size_t)n, 0, 64, ctx->stream));
+    int st = grow(ctx, ctx->sort_tmp, tb);
+    if (st) return st;
+    EV_OK(ctx, rocprim::radix_sort_pairs(ctx->sort_tmp.p, tb, (uint64_t *)keys.p, (uint64_t *)keys_s.p, (int *)idx.p,
+                                         (int *)idx_s.p, (size_t)n, 0, 64, ctx->stream));
+    return APD_OK;
+}
+
+static int elapsed(apd_eval_ctx *ctx, double &ms) {
+    float f = 0.0f;
+    EV_OK(ctx, hipEventElapsedTime(&f, ctx->ev0, ctx->ev1));
+    ms = (double)f;
+    return APD_OK;
+}
+
+// the largest float b with sqrtf(b) <= md (md >= 0, not NaN); +inf when there is no cut-off
+static float d2_bound(float md) {
+    const float inf = std::numeric_limits<float>::infinity();
+    if (md == inf) return inf;
+    float b = (float)((double)md * (double)md);
+    if (b == inf) b = std::numeric_limits<float>::max();
+    while (b > 0.0f && sqrtf(b) > md) b = std::nextafterf(b, 0.0f);
+    for (;;) {
+        const float nx = std::nextafterf(b, inf);
+        if (nx == inf || sqrtf(nx) > md) break;
+        b = nx;
+    }
+    return b;
+}
+
+extern "C" {
+
+apd_eval_ctx *apd_eval_create(int32_t device) {
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess || device < 0 || device >= n) return nullptr;
+    if (hipSetDevice(device) != hipSuccess) return nullptr;
+    auto *ctx = new apd_eval_ctx();
+    ctx->device = device;
+    if (hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking) != hipSuccess ||
+        hipEventCreate(&ctx->ev0) != hipSuccess || hipEventCreate(&ctx->ev1) != hipSuccess) {
+        apd_eval_destroy(ctx);
+        return nullptr;
+    }
+    return ctx;
+}
+
+void apd_eval_destroy(apd_eval_ctx *ctx) {
+    if (!ctx) return;
+    (void)hipSetDevice(ctx->device);
+    for (Buf *b : {&ctx->t_xyz, &ctx->t_keys, &ctx->t_keys_s, &ctx->t_idx, &ctx->t_idx_s, &ctx->t_pts, &ctx->t_boxes,
+                   &ctx->q_xyz, &ctx->q_keys, &ctx->q_keys_s, &ctx->q_idx, &ctx->q_idx_s, &ctx->q_dist, &ctx->q_aux,
+                   &ctx->sort_tmp, &ctx->small})
+        if (b->p) (void)hipFree(b->p);
+    if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
+    if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
+    if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
+    delete ctx;
+}
+
+const char *apd_eval_last_error(const apd_eval_ctx *ctx) {
+    return ctx ? ctx->err.c_str() : "apd_eval_create failed (no such HIP device)";
+}
+
+int32_t apd_eval_set_target(apd_eval_ctx *ctx, int64_t n64, const float *xyz) {
+    if (!ctx) return APD_EINVAL;
+    int st = check_n(ctx, "apd_eval_set_target", n64, xyz);
+    if (st) return st;
+    const int n = (int)n64;
+    ctx->build_ms = 0.0;
+    if (n == 0) {  // an empty target is a target: every distance is +inf
+        ctx->tree = Tree{};
+        ctx->has_target = true;
+        return APD_OK;
+    }
+    EV_OK(ctx, hipSetDevice(ctx->device));
+    ctx->has_target = false;
+    if ((st = grow(ctx, ctx->t_xyz, (size_t)n * 12)) || (st = grow(ctx, ctx->t_keys, (size_t)n * 8)) ||
+        (st = grow(ctx, ctx->t_keys_s, (size_t)n * 8)) || (st = grow(ctx, ctx->t_idx, (size_t)n * 4)) ||
+        (st = grow(ctx, ctx->t_idx_s, (size_t)n * 4)) || (st = grow(ctx, ctx->small, 256)))
+        return st;
+    hipStream_t s = ctx->stream;
+    EV_OK(ctx, hipMemcpyAsync(ctx->t_xyz.p, xyz, (size_t)n * 12, hipMemcpyDefault, s));
+    EV_OK(ctx, hipEventRecord(ctx->ev0, s));
+    uint32_t *bounds = (uint32_t *)ctx->small.p;
+    unsigned long long *counter = (unsigned long long *)((char *)ctx->small.p + 64);
+    EV_OK(ctx, hipMemsetAsync(bounds, 0xFF, 12, s));
+    EV_OK(ctx, hipMemsetAsync(bounds + 3, 0, 12, s));
+    EV_OK(ctx, hipMemsetAsync(counter, 0, 8, s));
+    hipLaunchKernelGGL(k_bounds, dim3(grid_capped(n)), dim3(BLOCK), 0, s, (const float *)ctx->t_xyz.p, n, bounds);
+    hipLaunchKernelGGL(k_morton_keys, dim3(grid_for(n)), dim3(BLOCK), 0, s, (const float *)ctx->t_xyz.p, n, bounds,
+                       (uint64_t *)ctx->t_keys.p, (int *)ctx->t_idx.p, counter);
+    EV_OK(ctx, hipGetLastError());
+    if ((st = sort_pairs(ctx, ctx->t_keys, ctx->t_keys_s, ctx->t_idx, ctx->t_idx_s, n))) return st;
+    unsigned long long nf64 = 0;
+    EV_OK(ctx, hipMemcpyAsync(&nf64, counter, 8, hipMemcpyDeviceToHost, s));
+    EV_OK(ctx, hipStreamSynchronize(s));
+    const int nf = (int)nf64;
+    Tree T{};
+    T.nf = nf;
+    if (nf > 0) {
+        int total = 0, c = (nf + LEAF - 1) / LEAF;
+        for (;;) {
+            T.off[T.levels] = total;
+            T.cnt[T.levels] = c;
+            total += c;
+            ++T.levels;
+            if (c == 1) break;
+            c = (c + FAN - 1) / FAN;
+        }
+        if ((st = grow(ctx, ctx->t_pts, (size_t)nf * 16)) || (st = grow(ctx, ctx->t_boxes, (size_t)total * 32)))
+            return st;
+        float4 *boxes = (float4 *)ctx->t_boxes.p;
+        hipLaunchKernelGGL(k_gather_points, dim3(grid_for(nf)), dim3(BLOCK), 0, s, (const float *)ctx->t_xyz.p,
+                           (const int *)ctx->t_idx_s.p, nf, (float4 *)ctx->t_pts.p);
+        hipLaunchKernelGGL(k_leaf_boxes, dim3(grid_for(T.cnt[0])), dim3(BLOCK), 0, s, (const float4 *)ctx->t_pts.p, nf,
+                           T.cnt[0], boxes);
+        for (int l = 1; l < T.levels; ++l)
+            hipLaunchKernelGGL(k_upper_boxes, dim3(grid_for(T.cnt[l])), dim3(BLOCK), 0, s,
+                               (const float4 *)(boxes + 2 * (size_t)T.off[l - 1]), T.cnt[l - 1], T.cnt[l],
+                               boxes + 2 * (size_t)T.off[l]);
+        EV_OK(ctx, hipGetLastError());
+        T.pts = (const float4 *)ctx->t_pts.p;
+        T.boxes = boxes;
+        T.keys = (const uint64_t *)ctx->t_keys_s.p;
+    }
+    EV_OK(ctx, hipEventRecord(ctx->ev1, s));
+    EV_OK(ctx, hipStreamSynchronize(s));
+    if ((st = elapsed(ctx, ctx->build_ms))) return st;
+    ctx->tree = T;
+    ctx->has_target = true;
+    return APD_OK;
+}
+
+int32_t apd_eval_distances(apd_eval_ctx *ctx, int64_t n64, const float *xyz, float max_dist, float *dist,
+                           int32_t num_tol, const float *tol, int64_t *within) {
+    if (!ctx) return APD_EINVAL;
+    int st = check_n(ctx, "apd_eval_distances", n64, xyz);
+    if (st) return st;
+    if (!(max_dist >= 0.0f)) {
+        ctx->err = "apd_eval_distances: max_dist is negative or NaN";
+        return APD_EINVAL;
+    }
+    if (num_tol < 0 || (num_tol > 0 && !tol)) {
+        ctx->err = "apd_eval_distances: bad tolerance list";
+        return APD_EINVAL;
+    }
+    if (!ctx->has_target) {
+        ctx->err = "apd_eval_distances: no target set";
+        return APD_ESTATE;
+    }
+    EV_OK(ctx, hipSetDevice(ctx->device));
+    std::vector<float> tols((size_t)num_tol);
+    if (num_tol > 0) EV_OK(ctx, hipMemcpy(tols.data(), tol, (size_t)num_tol * 4, hipMemcpyDefault));
+    for (float t : tols)
+        if (!(t >= 0.0f) || t > max_dist) {
+            ctx->err = "apd_eval_distances: a tolerance is negative, NaN or above max_dist";
+            return APD_EINVAL;
+        }
+    const int n = (int)n64;
+    ctx->query_ms = 0.0;
+    std::vector<unsigned long long> counts((size_t)num_tol, 0ull);
+    if (n == 0) {
+        if (within && num_tol > 0)
+            EV_OK(ctx, hipMemcpy(within, counts.data(), (size_t)num_tol * 8, hipMemcpyDefault));
+        return APD_OK;
+    }
+    const int ncnt = within ? num_tol : 0;
+    if ((st = grow(ctx, ctx->q_xyz, (size_t)n * 12)) || (st = grow(ctx, ctx->q_keys, (size_t)n * 8)) ||
+        (st = grow(ctx, ctx->q_keys_s, (size_t)n * 8)) || (st = grow(ctx, ctx->q_idx, (size_t)n * 4)) ||
+        (st = grow(ctx, ctx->q_idx_s, (size_t)n * 4)) || (st = grow(ctx, ctx->q_dist, (size_t)n * 4)) ||
+        (st = grow(ctx, ctx->q_aux, (size_t)std::max(ncnt, 1) * 8)) || (st = grow(ctx, ctx->small, 256)))
+        return st;
+    hipStream_t s = ctx->stream;
+    EV_OK(ctx, hipMemcpyAsync(ctx->q_xyz.p, xyz, (size_t)n * 12, hipMemcpyDefault, s));
+    EV_OK(ctx, hipEventRecord(ctx->ev0, s));
+    // queries are keyed over the TARGET's bounding box, still in `small` from set_target (an all-
+    // non-finite or empty target leaves no usable box: every key is then 0 or NONE, which is fine)
+    const uint32_t *bounds = (const uint32_t *)ctx->small.p;
+    hipLaunchKernelGGL(k_morton_keys, dim3(grid_for(n)), dim3(BLOCK), 0, s, (const float *)ctx->q_xyz.p, n, bounds,
+                       (uint64_t *)ctx->q_keys.p, (int *)ctx->q_idx.p, (unsigned long long *)nullptr);
+    EV_OK(ctx, hipGetLastError());
+    if ((st = sort_pairs(ctx, ctx->q_keys, ctx->q_keys_s, ctx->q_idx, ctx->q_idx_s, n))) return st;
+    hipLaunchKernelGGL(k_nearest, dim3(grid_for(n)), dim3(BLOCK), 0, s, ctx->tree, n,
+                       (const uint64_t *)ctx->q_keys_s.p, (const int *)ctx->q_idx_s.p, (const float *)ctx->q_xyz.p,
+                       d2_bound(max_dist), max_dist, (float *)ctx->q_dist.p);
+    EV_OK(ctx, hipGetLastError());
+    if (ncnt > 0) {
+        EV_OK(ctx, hipMemsetAsync(ctx->q_aux.p, 0, (size_t)ncnt * 8, s));
+        for (int k0 = 0; k0 < ncnt; k0 += TOL_CHUNK) {
+            TolChunk tc{};
+            tc.n = std::min(TOL_CHUNK, ncnt - k0);
+            for (int k = 0; k < tc.n; ++k) tc.tol[k] = tols[(size_t)(k0 + k)];
+            hipLaunchKernelGGL(k_count_within, dim3(grid_capped(n)), dim3(BLOCK), 0, s, (const float *)ctx->q_dist.p,
+                               n, tc, (unsigned long long *)ctx->q_aux.p + k0);
+        }
+        EV_OK(ctx, hipGetLastError());
+    }
+    EV_OK(ctx, hipEventRecord(ctx->ev1, s));
+    if (dist) EV_OK(ctx, hipMemcpyAsync(dist, ctx->q_dist.p, (size_t)n * 4, hipMemcpyDefault, s));
+    if (ncnt > 0) EV_OK(ctx, hipMemcpyAsync(within, ctx->q_aux.p, (size_t)ncnt * 8, hipMemcpyDefault, s));
+    EV_OK(ctx, hipStreamSynchronize(s));
+    return elapsed(ctx, ctx->query_ms);
+}
+
+int32_t apd_eval_voxel_downsample(apd_eval_ctx *ctx, int64_t n64, const float *xyz, float voxel, int32_t *keep_idx,
+                                  int64_t *n_keep) {
+    if (!ctx) return APD_EINVAL;
+    int st = check_n(ctx, "apd_eval_voxel_downsample", n64, xyz);
+    if (st) return st;
+    if (!(voxel > 0.0f) || !std::isfinite(voxel)) {
+        ctx->err = "apd_eval_voxel_downsample: voxel must be positive and finite";
+        return APD_EINVAL;
+    }
+    if (!n_keep || (n64 > 0 && !keep_idx)) {
+        ctx->err = "apd_eval_voxel_downsample: NULL output";
+        return APD_EINVAL;
+    }
+    EV_OK(ctx, hipSetDevice(ctx->device));
+    const int n = (int)n64;
+    ctx->voxel_ms = 0.0;
+    unsigned long long kept = 0;
+    if (n == 0) {
+        EV_OK(ctx, hipMemcpy(n_keep, &kept, 8, hipMemcpyDefault));
+        return APD_OK;
+    }
+    // q_dist holds the head flags, q_aux their exclusive scan, q_keys (reused) the kept indices
+    if ((st = grow(ctx, ctx->q_xyz, (size_t)n * 12)) || (st = grow(ctx, ctx->q_keys, (size_t)n * 8)) ||
+        (st = grow(ctx, ctx->q_keys_s, (size_t)n * 8)) || (st = grow(ctx, ctx->q_idx, (size_t)n * 4)) ||
+        (st = grow(ctx, ctx->q_idx_s, (size_t)n * 4)) || (st = grow(ctx, ctx->q_dist, (size_t)n * 4)) ||
+        (st = grow(ctx, ctx->q_aux, 128 + (size_t)n * 4)))
+        return st;
+    // q_aux: bounds at byte 0, the kept count at byte 64, the scan from byte 128. Its own scratch for the bounds: `small` keeps the target's box for apd_eval_distances
+    uint32_t *bounds = (uint32_t *)ctx->q_aux.p;
+    unsigned long long *counter = (unsigned long long *)((char *)ctx->q_aux.p + 64);
+    hipStream_t s = ctx->stream;
+    EV_OK(ctx, hipMemcpyAsync(ctx->q_xyz.p, xyz, (size_t)n * 12, hipMemcpyDefault, s));
+    EV_OK(ctx, hipEventRecord(ctx->ev0, s));
+    EV_OK(ctx, hipMemsetAsync(bounds, 0xFF, 12, s));
+    EV_OK(ctx, hipMemsetAsync(bounds + 3, 0, 12, s));
+    hipLaunchKernelGGL(k_voxel_bounds, dim3(grid_capped(n)), dim3(BLOCK), 0, s, (const float *)ctx->q_xyz.p, n, voxel,
+                       bounds);
+    EV_OK(ctx, hipGetLastError());
+    uint32_t hb[6];
+    EV_OK(ctx, hipMemcpyAsync(hb, bounds, 24, hipMemcpyDeviceToHost, s));
+    EV_OK(ctx, hipStreamSynchronize(s));
+    if (hb[0] == 0xFFFFFFFFu) {  // no finite point
+        EV_OK(ctx, hipMemcpy(n_keep, &kept, 8, hipMemcpyDefault));
+        return APD_OK;
+    }
+    float mn[3];
+    for (int a = 0; a < 3; ++a) {
+        auto dec = [](uint32_t u) {
+            const uint32_t b = (u & 0x80000000u) ? (u & 0x7FFFFFFFu) : ~u;
+            float f;
+            memcpy(&f, &b, 4);
+            return f;
+        };
+        mn[a] = dec(hb[a]);
+        const double span = (double)dec(hb[3 + a]) - (double)mn[a];
+        if (!(span < 2097152.0)) {
+            ctx->err = "apd_eval_voxel_downsample: an axis spans more than 2^21 voxels";
+            return APD_EINVAL;
+        }
+    }
+    hipLaunchKernelGGL(k_voxel_keys, dim3(grid_for(n)), dim3(BLOCK), 0, s, (const float *)ctx->q_xyz.p, n, voxel,
+                       mn[0], mn[1], mn[2], (uint64_t *)ctx->q_keys.p, (int *)ctx->q_idx.p);
+    EV_OK(ctx, hipGetLastError());
+    if ((st = sort_pairs(ctx, ctx->q_keys, ctx->q_keys_s, ctx->q_idx, ctx->q_idx_s, n))) return st;
+    int *flag = (int *)ctx->q_dist.p, *pos = (int *)ctx->q_aux.p + 32, *keep = (int *)ctx->q_keys.p;
+    EV_OK(ctx, hipMemsetAsync(flag, 0, (size_t)n * 4, s));
+    hipLaunchKernelGGL(k_voxel_heads, dim3(grid_for(n)), dim3(BLOCK), 0, s, (const uint64_t *)ctx->q_keys_s.p,
+                       (const int *)ctx->q_idx_s.p, n, flag);
+    EV_OK(ctx, hipGetLastError());
+    size_t tb = 0;
+    EV_OK(ctx, rocprim::exclusive_scan(nullptr, tb, flag, pos, 0, (size_t)n, rocprim::plus<int>(), s));
+    if ((st = grow(ctx, ctx->sort_tmp, tb))) return st;
+    EV_OK(ctx, rocprim::exclusive_scan(ctx->sort_tmp.p, tb, flag, pos, 0, (size_t)n, rocprim::plus<int>(), s));
+    hipLaunchKernelGGL(k_voxel_compact, dim3(grid_for(n)), dim3(BLOCK), 0, s, (const int *)flag, (const int *)pos, n,
+                       keep, counter);
+    EV_OK(ctx, hipGetLastError());
+    EV_OK(ctx, hipEventRecord(ctx->ev1, s));
+    EV_OK(ctx, hipMemcpyAsync(&kept, counter, 8, hipMemcpyDeviceToHost, s));
+    EV_OK(ctx, hipStreamSynchronize(s));
+    if (kept > 0) EV_OK(ctx, hipMemcpy(keep_idx, keep, (size_t)kept * 4, hipMemcpyDefault));
+    EV_OK(ctx, hipMemcpy(n_keep, &kept, 8, hipMemcpyDefault));
+    return elapsed(ctx, ctx->voxel_ms);
+}
+
+int32_t apd_eval_get_timing(apd_eval_ctx *ctx, double *build_ms, double *query_ms, double *voxel_ms) {
+    if (!ctx) return APD_EINVAL;
+    if (build_ms) *build_ms = ctx->build_ms;
+    if (query_ms) *query_ms = ctx->query_ms;
+    if (voxel_ms) *voxel_ms = ctx->voxel_ms;
+    return APD_OK;
+}
+
+}  // extern "C"

@@ -6,6 +6,8 @@
 
 #include <sys/stat.h>
 
+#include <algorithm>
+#include <climits>
 #include <cstdio>
 #include <cstring>
 #include <fstream>
@@ -212,6 +214,107 @@ bool read_camera(const std::string &path, apd_camera &cam) {
     if (!(in >> cam.depth_num >> cam.depth_max)) {
         cam.depth_num = 192;
         cam.depth_max = cam.interval * cam.depth_num + cam.depth_min;
+    }
+    return true;
+}
+
+namespace {
+int ply_type_size(const std::string &t) {
+    static const std::map<std::string, int> sizes = {
+        {"char", 1},  {"uchar", 1},  {"int8", 1},  {"uint8", 1},   {"short", 2},  {"ushort", 2},
+        {"int16", 2}, {"uint16", 2}, {"int", 4},   {"uint", 4},    {"int32", 4},  {"uint32", 4},
+        {"float", 4}, {"float32", 4}, {"double", 8}, {"float64", 8}};
+    auto it = sizes.find(t);
+    return it == sizes.end() ? 0 : it->second;
+}
+}  // namespace
+
+bool read_ply_xyz(const std::string &path, std::vector<float> &xyz, std::string &err) {
+    xyz.clear();
+    std::ifstream in(path, std::ios::binary);
+    if (!in) { err = "cannot open " + path; return false; }
+    auto fail = [&](const std::string &what) { err = path + ": " + what; return false; };
+    std::string line;
+    auto next_line = [&]() {
+        if (!std::getline(in, line) || line.size() > 4096) return false;
+        if (!line.empty() && line.back() == '\r') line.pop_back();
+        return true;
+    };
+    if (!next_line() || line != "ply") return fail("not a PLY file");
+    bool have_format = false, in_vertex = false, seen_vertex = false, ended = false;
+    uint64_t count = 0;
+    size_t stride = 0;
+    long off[3] = {-1, -1, -1};
+    for (int lines = 0; lines < 100000 && next_line(); ++lines) {
+        std::istringstream ls(line);
+        std::string kw;
+        ls >> kw;
+        if (kw == "end_header") { ended = true; break; }
+        if (kw.empty() || kw == "comment" || kw == "obj_info") continue;
+        if (kw == "format") {
+            std::string fmt, ver;
+            ls >> fmt >> ver;
+            if (fmt != "binary_little_endian" || ver != "1.0")
+                return fail("unsupported format '" + fmt + " " + ver + "' (binary_little_endian 1.0 only)");
+            have_format = true;
+        } else if (kw == "element") {
+            std::string name;
+            std::string num;
+            ls >> name >> num;
+            in_vertex = false;
+            if (name == "vertex") {
+                if (seen_vertex) return fail("more than one vertex element");
+                if (num.empty() || num.size() > 18 || num.find_first_not_of("0123456789") != std::string::npos)
+                    return fail("bad vertex count");
+                count = std::stoull(num);
+                seen_vertex = in_vertex = true;
+            } else if (!seen_vertex) {
+                return fail("element '" + name + "' in front of vertex");
+            }
+        } else if (kw == "property") {
+            if (!in_vertex) {
+                if (!seen_vertex) return fail("property outside an element");
+                continue;  // a later element's: ignored
+            }
+            std::string type, name;
+            ls >> type >> name;
+            if (type == "list") return fail("list property on vertex");
+            const int sz = ply_type_size(type);
+            if (sz == 0 || name.empty()) return fail("unknown property type '" + type + "'");
+            for (int a = 0; a < 3; ++a)
+                if (name == std::string(1, "xyz"[a])) {
+                    if (sz != 4 || (type != "float" && type != "float32")) return fail(name + " is not float");
+                    if (off[a] >= 0) return fail("duplicate property " + name);
+                    off[a] = (long)stride;
+                }
+            stride += (size_t)sz;
+            if (stride > 65536) return fail("vertex record too large");
+        } else {
+            return fail("unexpected header line '" + kw + "'");
+        }
+    }
+    if (!ended) return fail("header has no end_header");
+    if (!have_format) return fail("header has no format line");
+    if (!seen_vertex) return fail("no vertex element");
+    for (int a = 0; a < 3; ++a)
+        if (off[a] < 0) return fail(std::string("vertex has no property ") + "xyz"[a]);
+    // the body must be in the file before anything of its size is allocated
+    const std::streampos here = in.tellg();
+    in.seekg(0, std::ios::end);
+    const std::streamoff avail = in.tellg() - here;
+    in.seekg(here);
+    if (here < 0 || avail < 0 || count > (uint64_t)avail / stride) return fail("vertex count exceeds the file's size");
+    if (count > (uint64_t)INT32_MAX) return fail("more than 2^31-1 vertices");
+    xyz.resize((size_t)count * 3);
+    const size_t chunk = std::max<size_t>(1, ((size_t)4 << 20) / stride);
+    std::vector<char> buf(chunk * stride);
+    for (size_t done = 0; done < count;) {
+        const size_t m = std::min<size_t>(chunk, (size_t)count - done);
+        in.read(buf.data(), (std::streamsize)(m * stride));
+        if (!in) { xyz.clear(); return fail("truncated body"); }
+        for (size_t i = 0; i < m; ++i)
+            for (int a = 0; a < 3; ++a) memcpy(&xyz[3 * (done + i) + a], &buf[i * stride + (size_t)off[a]], 4);
+        done += m;
     }
     return true;
 }

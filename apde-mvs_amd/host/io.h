@@ -96,6 +96,15 @@ struct Problem {  // main.h:102-115
 // is the first of .jpg .png .jpeg .JPG .PNG .JPEG present for the reference image.
 bool read_pair_file(const std::string &dense_folder, std::vector<Problem> &problems, std::string &err);
 
+// Vertex positions of a binary_little_endian 1.0 PLY (APD.ply's 12- and 15-byte records among
+// others): one `vertex` element with scalar properties of any standard type in any order, of which
+// x, y and z must be `float`; the other properties are skipped by size, `comment` and `obj_info`
+// lines are accepted and elements after `vertex` are ignored. Rejected with a message in `err`,
+// before anything is allocated from the header's count: ascii and big-endian files, a list
+// property on `vertex`, an element in front of `vertex`, a missing coordinate, and a vertex count
+// the file does not hold.
+bool read_ply_xyz(const std::string &path, std::vector<float> &xyz, std::string &err);
+
 std::string format_index(int id);  // ToFormatIndex: %08d
 bool file_exists(const std::string &p);
 bool make_dir(const std::string &p);

@@ -146,7 +146,9 @@ def worker(args, scan):
         if args.resume and os.path.exists(os.path.join(apd_dir, 'APD.ply')):
             print('APD result exists for {}'.format(scan_dir), flush=True)
             return 0
-        print(cmd, flush=True)
+        # one write per line: print() writes the text and the newline separately, and two slots
+        # printing at once could put two commands on one line
+        print(cmd + '\n', end='', flush=True)
         if args.review:
             return 0
         return subprocess.run(cmd, shell=True).returncode

@@ -347,3 +347,33 @@ def read_bin_mat(path: str) -> np.ndarray:
         dt, ch = {0: (np.uint8, 1), 4: (np.int32, 1), 5: (np.float32, 1), 21: (np.float32, 3)}[cvt]
         data = np.frombuffer(fh.read(), dt)
     return data.reshape((rows, cols) if ch == 1 else (rows, cols, ch)).copy()
+
+
+def gt_cloud(scene: Scene) -> np.ndarray:
+    """Every gt_depth > 0 pixel of every view back-projected to world coordinates (float64 arithmetic:
+    X = C + d * R^T K^-1 (x, y, 1), d the camera-frame z the renderer stored), as float32 (n, 3)."""
+    xs, ys = np.meshgrid(np.arange(scene.width, dtype=np.float64), np.arange(scene.height, dtype=np.float64))
+    out = []
+    for cam, depth in zip(scene.cameras, scene.gt_depth):
+        m = depth > 0
+        pix = np.stack([xs[m], ys[m], np.ones(int(m.sum()))], axis=0)
+        rays = (cam.R.T @ np.linalg.inv(cam.K)) @ pix
+        out.append((cam.center[:, None] + rays * depth[m].astype(np.float64)[None, :]).T)
+    return np.concatenate(out).astype(np.float32) if out else np.zeros((0, 3), np.float32)
+
+
+def write_ply(path: str, xyz: np.ndarray) -> None:
+    """binary_little_endian PLY with float x, y, z only (APD.ply's 12-byte records)."""
+    a = np.ascontiguousarray(xyz, "<f4").reshape(-1, 3)
+    with open(path, "wb") as fh:
+        fh.write(("ply\nformat binary_little_endian 1.0\nelement vertex %d\nproperty float x\nproperty float y\n"
+                  "property float z\nend_header\n" % len(a)).encode())
+        fh.write(a.tobytes())
+
+
+def write_gt_depths(scene: Scene, folder: str) -> None:
+    """<id>.bin CV_32FC1 bin-mats of the ground-truth depth maps (0 = no surface), the layout
+    `apd_eval --gt_depth` reads."""
+    os.makedirs(folder, exist_ok=True)
+    for i, d in enumerate(scene.gt_depth):
+        write_bin_mat(os.path.join(folder, f"{i:08d}.bin"), np.ascontiguousarray(d, np.float32))
