@@ -101,7 +101,7 @@ def _ptr(a, ctype):
     return a.ctypes.data_as(C.POINTER(ctype))
 
 
-_TORCH_DTYPES = {np.dtype(np.float32): "float32", np.dtype(np.uint8): "uint8"}
+_TORCH_DTYPES = {np.dtype(np.float32): "float32", np.dtype(np.uint8): "uint8", np.dtype(np.int32): "int32"}
 
 
 def _torch_device_sync(*objs):
@@ -231,7 +231,23 @@ EXPORTS = ["apd_abi_version", "apd_device_count", "apd_create", "apd_destroy", "
 
 # include/apd_eval.h: its own list (EXPORTS is the apd_hip.h + apd_fusion.h set apd_abi_version() covers)
 EVAL_EXPORTS = ["apd_eval_create", "apd_eval_destroy", "apd_eval_last_error", "apd_eval_set_target",
-                "apd_eval_distances", "apd_eval_voxel_downsample", "apd_eval_get_timing"]
+                "apd_eval_distances", "apd_eval_voxel_downsample", "apd_eval_get_timing",
+                "apd_eval_render_depth", "apd_eval_visibility", "apd_eval_get_render_timing"]
+
+
+def camera_from_values(v) -> ApdCamera:
+    """ApdCamera from a dict of its field values (synth.camera_struct_values)."""
+    cam = ApdCamera()
+    for name in ("K", "R", "t", "c"):
+        if name in v:
+            a = np.asarray(v[name], np.float32).ravel()
+            setattr(cam, name, (C.c_float * len(a))(*[float(x) for x in a]))
+    for name in ("height", "width"):
+        setattr(cam, name, int(v[name]))
+    for name in ("depth_min", "depth_max", "interval", "depth_num"):
+        if name in v:
+            setattr(cam, name, float(v[name]))
+    return cam
 
 
 class ApdFusionView(C.Structure):  # include/apd_fusion.h
@@ -336,6 +352,14 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     lib.apd_eval_get_timing.restype = C.c_int32
     lib.apd_eval_get_timing.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double),
                                         C.POINTER(C.c_double)]
+    lib.apd_eval_render_depth.restype = C.c_int32
+    lib.apd_eval_render_depth.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.POINTER(ApdCamera),
+                                          C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
+    lib.apd_eval_visibility.restype = C.c_int32
+    lib.apd_eval_visibility.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.POINTER(ApdCamera),
+                                        C.POINTER(C.c_void_p), C.c_float, C.c_void_p, C.c_void_p]
+    lib.apd_eval_get_render_timing.restype = C.c_int32
+    lib.apd_eval_get_render_timing.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     return lib
 
 
@@ -486,6 +510,85 @@ class EvalEngine:
         self._check(self.lib.apd_eval_get_timing(self.ctx, C.byref(b), C.byref(q), C.byref(v)), "apd_eval_get_timing")
         return {"build_ms": b.value, "query_ms": q.value, "voxel_ms": v.value}
 
+    @staticmethod
+    def _cams(cams):
+        """ApdCamera array from ApdCamera structures or dicts of their field values
+        (synth.camera_struct_values)."""
+        arr = (ApdCamera * max(len(cams), 1))()
+        for i, c in enumerate(cams):
+            if isinstance(c, ApdCamera):
+                arr[i] = c
+            else:
+                arr[i] = camera_from_values(c)
+        return arr
+
+    def render_depth_ptr(self, n: int, xyz_ptr, cams, splat: int, depth_ptrs, index_ptrs=None):
+        """depth_ptrs / index_ptrs: one address (or None) per view; index_ptrs itself may be None."""
+        arr = cams if isinstance(cams, C.Array) else self._cams(cams)
+        nv = len(depth_ptrs)
+        dp = (C.c_void_p * max(nv, 1))(*depth_ptrs)
+        ip = None if index_ptrs is None else (C.c_void_p * max(nv, 1))(*index_ptrs)
+        self._check(self.lib.apd_eval_render_depth(self.ctx, n, xyz_ptr, nv, arr, splat, dp, ip),
+                    "apd_eval_render_depth")
+
+    def render_depth(self, xyz, cams, splat: int = 0, want_index: bool = False):
+        """z-buffer of the cloud in every camera: a list of (H, W) float32 depth maps (0 = nothing
+        projects), or with want_index a list of (depth, index) pairs, index int32 with -1 there."""
+        a, n, addr, dev = self._cloud(xyz)
+        arr = self._cams(cams)
+        shapes = [(int(arr[i].height), int(arr[i].width)) for i in range(len(cams))]
+        if dev:
+            import torch
+            depth = [torch.empty(s, dtype=torch.float32, device=a.device) for s in shapes]
+            index = [torch.empty(s, dtype=torch.int32, device=a.device) for s in shapes] if want_index else None
+            _torch_device_sync(a, depth, index)
+            addr_of = lambda t: t.data_ptr()
+        else:
+            depth = [np.empty(s, np.float32) for s in shapes]
+            index = [np.empty(s, np.int32) for s in shapes] if want_index else None
+            addr_of = lambda t: t.ctypes.data
+        self.render_depth_ptr(n, addr, arr, splat, [addr_of(d) for d in depth],
+                              None if index is None else [addr_of(i) for i in index])
+        return list(zip(depth, index)) if want_index else depth
+
+    def visibility_ptr(self, n: int, xyz_ptr, cams, depth_ptrs, rel_tol: float, seen_ptr) -> int:
+        arr = cams if isinstance(cams, C.Array) else self._cams(cams)
+        nv = len(depth_ptrs)
+        dp = (C.c_void_p * max(nv, 1))(*depth_ptrs)
+        n_any = C.c_int64(0)
+        self._check(self.lib.apd_eval_visibility(self.ctx, n, xyz_ptr, nv, arr, dp, rel_tol, seen_ptr,
+                                                 C.addressof(n_any)), "apd_eval_visibility")
+        return n_any.value
+
+    def visibility(self, xyz, cams, depths, rel_tol: float, want_any: bool = False):
+        """seen int32[n]: in how many of the views point i passes the z-buffer test against depths[v]
+        (an (H, W) float32 map per camera, numpy or torch). With want_any: (seen, #{seen > 0})."""
+        a, n, addr, dev = self._cloud(xyz)
+        arr = self._cams(cams)
+        if len(depths) != len(cams):
+            raise ValueError("one depth map per camera")
+        maps = [_keep(d, np.float32) for d in depths]
+        for i, m in enumerate(maps):
+            if tuple(m.shape) != (int(arr[i].height), int(arr[i].width)):
+                raise ValueError(f"depth map {i} has shape {tuple(m.shape)}, its camera {arr[i].height}x{arr[i].width}")
+        if dev:
+            import torch
+            seen = torch.empty(n, dtype=torch.int32, device=a.device)
+            sptr = seen.data_ptr() if n else None
+        else:
+            seen = np.empty(n, np.int32)
+            sptr = seen.ctypes.data if n else None
+        _torch_device_sync(a, seen, maps)
+        ptrs = [m.data_ptr() if hasattr(m, "data_ptr") else m.ctypes.data for m in maps]
+        n_any = self.visibility_ptr(n, addr, arr, ptrs, rel_tol, sptr)
+        return (seen, n_any) if want_any else seen
+
+    def render_timing(self) -> dict:
+        r, v = C.c_double(), C.c_double()
+        self._check(self.lib.apd_eval_get_render_timing(self.ctx, C.byref(r), C.byref(v)),
+                    "apd_eval_get_render_timing")
+        return {"render_ms": r.value, "visibility_ms": v.value}
+
     def close(self):
         if self.ctx:
             self.lib.apd_eval_destroy(self.ctx)
@@ -502,13 +605,23 @@ ETH3D_TOLERANCES = (0.01, 0.02, 0.05, 0.1, 0.2, 0.5)  # the ones tools/eval_eth_
 
 
 def cloud_metrics(rec_xyz, gt_xyz, tolerances=ETH3D_TOLERANCES, max_dist=None, voxel: float = 0.0,
-                  engine: Optional[EvalEngine] = None) -> dict:
+                  engine: Optional[EvalEngine] = None, gt_cams=None, min_views: int = 1, splat: int = 0,
+                  occlusion_tol: float = 0.01) -> dict:
     """Accuracy / completeness / F1 of a reconstructed cloud against a ground-truth cloud (numpy
     (n, 3) float32), the definitions the `apd_eval` command line shares: R and G are the clouds after
     dropping non-finite points and, for voxel > 0, down-sampling each on its own; accuracy =
     #{dist(R_i, G) <= t} / |R|, completeness = #{dist(G_j, R) <= t} / |G|, F1 = 2ac / (a + c), each
     ratio 0 when its denominator is 0. Plain nearest-neighbour distances truncated at max_dist
-    (default: the largest tolerance); no free-space or visibility modelling."""
+    (default: the largest tolerance); no free-space or visibility modelling.
+
+    With gt_cams (ApdCamera structures or dicts of their values) completeness is measured over G',
+    the points of G that pass a z-buffer test in at least min_views of those cameras: G itself is
+    rendered into every camera (footprint `splat`), and a point is seen in a view when it projects
+    into the image no deeper than (1 + occlusion_tol) times the rendered depth there. Accuracy is
+    still measured against all of G: a reconstructed point near an unseen part of the scan is not an
+    error. gt["points_visible"] = |G'|. A z-buffer test, not the ETH3D tool's free-space model."""
+    if gt_cams is not None and min_views < 1:
+        raise ValueError("min_views must be at least 1")
     tol = np.ascontiguousarray(tolerances, np.float32).reshape(-1)
     md = float(tol.max()) if max_dist is None else float(np.float32(max_dist))
     eng = engine or EvalEngine()
@@ -525,8 +638,19 @@ def cloud_metrics(rec_xyz, gt_xyz, tolerances=ETH3D_TOLERANCES, max_dist=None, v
             info["points"] = int(len(a))
             clouds[name] = a
             out[name] = info
+        if gt_cams is not None:
+            g = clouds["gt"]
+            seen = eng.visibility(g, gt_cams, eng.render_depth(g, gt_cams, splat), occlusion_tol)
+            tr = eng.render_timing()
+            clouds["gt_visible"] = np.ascontiguousarray(g[seen >= min_views])
+            out["gt"]["points_visible"] = int(len(clouds["gt_visible"]))
+            out["visibility"] = {"views": len(gt_cams), "min_views": int(min_views), "splat": int(splat),
+                                 "occlusion_tol": float(np.float32(occlusion_tol))}
+            out["timing_ms"]["visibility"] = tr
+        else:
+            clouds["gt_visible"] = clouds["gt"]
         ratios = {}
-        for name, q, t in (("accuracy", "rec", "gt"), ("completeness", "gt", "rec")):
+        for name, q, t in (("accuracy", "rec", "gt"), ("completeness", "gt_visible", "rec")):
             eng.set_target(clouds[t])
             dist, within = eng.distances(clouds[q], md, tol)
             tm = eng.timing()

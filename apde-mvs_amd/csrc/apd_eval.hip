@@ -1,5 +1,6 @@
 // apd_eval.hip — device side of the point-cloud evaluation (include/apd_eval.h): truncated
-// nearest-neighbour distances between two clouds and voxel down-sampling.
+// nearest-neighbour distances between two clouds, voxel down-sampling, and a z-buffer renderer of a
+// cloud into cameras with a per-point visibility count (integer atomics: deterministic).
 //
 // Search structure: a Morton-sorted implicit bounding-volume tree.
 //   - finite targets are quantised to 21 bits per axis over their bounding box (in double) and sorted
@@ -17,6 +18,7 @@
 
 #include <cmath>
 #include <cstdint>
+#include <cstdlib>
 #include <cstring>
 #include <limits>
 #include <string>
@@ -350,6 +352,108 @@ __global__ void __launch_bounds__(BLOCK) k_voxel_compact(const int *__restrict__
     if (i == n - 1) *n_keep = (unsigned long long)(pos[i] + flag[i]);
 }
 
+// ---- z-buffer rendering and visibility ------------------------------------------------------------
+
+constexpr uint64_t PIX_EMPTY = ~0ull;  // above every key: the depth word of a key is below 0x7F800000
+constexpr int VIS_CHUNK = 8;           // views per visibility launch (their cameras travel as kernel arguments)
+
+// int(v) as x86-64 cvttss2si, restated from csrc/apd_fusion.hip (trunc_x86).
+__device__ __forceinline__ int trunc_x86(float v) {
+    if (!(v >= -2147483648.0f && v < 2147483648.0f)) return INT32_MIN;
+    return (int)v;
+}
+
+// The render / visibility contract of include/apd_eval.h: project() of csrc/apd_fusion.hip
+// (ProjectCamera, APD.cpp:891-900) restated statement for statement, then the rounding its callers
+// apply. Returns false for a point that takes no part in the view.
+__device__ __forceinline__ bool project_point(const apd_camera &cam, float x, float y, float z, float &d, int &u,
+                                              int &v) {
+    if (!finite3(x, y, z)) return false;
+    const float tx = cam.R[0] * x + cam.R[1] * y + cam.R[2] * z + cam.t[0];
+    const float ty = cam.R[3] * x + cam.R[4] * y + cam.R[5] * z + cam.t[1];
+    const float tz = cam.R[6] * x + cam.R[7] * y + cam.R[8] * z + cam.t[2];
+    d = cam.K[6] * tx + cam.K[7] * ty + cam.K[8] * tz;
+    if (!(d > 0.0f && d < __uint_as_float(0x7F800000u))) return false;
+    const float px = (cam.K[0] * tx + cam.K[1] * ty + cam.K[2] * tz) / d;
+    const float py = (cam.K[3] * tx + cam.K[4] * ty + cam.K[5] * tz) / d;
+    u = trunc_x86(px + 0.5f);
+    v = trunc_x86(py + 0.5f);
+    return true;
+}
+
+// One lane per point; the camera is a kernel argument, so its 21 floats come by scalar loads.
+// order == nullptr: lane j takes point j; otherwise point order[j] (the Morton order of the cloud).
+// Every covered pixel takes the minimum of (bits(d) << 32) | i: d > 0, so its bits order like d, and
+// the low word breaks ties towards the lowest point index. The plain load in front of the atomic
+// may be stale, but a pixel's key only ever decreases, so a stale value is >= the current one and
+// skipping on key >= loaded never drops a key that would have won.
+__global__ void __launch_bounds__(BLOCK) k_splat(const float *__restrict__ xyz, const int *__restrict__ order, int n,
+                                                 const apd_camera cam, int splat, uint64_t *keys) {
+    const int j = blockIdx.x * BLOCK + threadIdx.x;
+    if (j >= n) return;
+    const int i = order ? order[j] : j;
+    float d;
+    int u, v;
+    if (!project_point(cam, xyz[3 * (size_t)i], xyz[3 * (size_t)i + 1], xyz[3 * (size_t)i + 2], d, u, v)) return;
+    const int W = cam.width, H = cam.height;
+    // in 64 bits: u or v may be INT32_MIN (covers nothing) or anywhere else in the int range
+    const int64_t a0 = max((int64_t)u - splat, (int64_t)0), a1 = min((int64_t)u + splat, (int64_t)W - 1);
+    const int64_t b0 = max((int64_t)v - splat, (int64_t)0), b1 = min((int64_t)v + splat, (int64_t)H - 1);
+    if (a0 > a1 || b0 > b1) return;
+    const uint64_t key = (uint64_t)__float_as_uint(d) << 32 | (uint32_t)i;
+    for (int b = (int)b0; b <= (int)b1; ++b)
+        for (int a = (int)a0; a <= (int)a1; ++a) {
+            uint64_t *p = keys + ((size_t)b * W + a);
+            if (key >= __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT)) continue;
+            (void)__hip_atomic_fetch_min(p, key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // no-return umin
+        }
+}
+
+// One lane per pixel: unpack the key plane.
+__global__ void __launch_bounds__(BLOCK) k_resolve(const uint64_t *__restrict__ keys, int npix, float *depth,
+                                                   int *index) {
+    const int p = blockIdx.x * BLOCK + threadIdx.x;
+    if (p >= npix) return;
+    const uint64_t k = keys[p];
+    const bool hit = k != PIX_EMPTY;
+    depth[p] = hit ? __uint_as_float((uint32_t)(k >> 32)) : 0.0f;
+    if (index) index[p] = hit ? (int)(uint32_t)k : -1;
+}
+
+struct VisViews {
+    apd_camera cam[VIS_CHUNK];
+    const float *depth[VIS_CHUNK];
+    int n;
+};
+
+// One lane per point, a loop over the chunk's views with one gather each, one int32 store per point.
+// first: this launch starts the count, otherwise it adds to the earlier chunks'. n_any (last chunk
+// only): #{seen > 0}, a ballot and one integer atomic per wave.
+__global__ void __launch_bounds__(BLOCK) k_visibility(const float *__restrict__ xyz, int n, const VisViews vv,
+                                                      float factor, int first, int *seen,
+                                                      unsigned long long *n_any) {
+    const int i = blockIdx.x * BLOCK + threadIdx.x;
+    int cnt = 0;
+    if (i < n) {
+        const float x = xyz[3 * (size_t)i], y = xyz[3 * (size_t)i + 1], z = xyz[3 * (size_t)i + 2];
+        for (int k = 0; k < vv.n; ++k) {
+            const apd_camera &cam = vv.cam[k];
+            float d;
+            int u, v;
+            if (!project_point(cam, x, y, z, d, u, v)) continue;
+            if (u < 0 || u >= cam.width || v < 0 || v >= cam.height) continue;
+            const float zb = vv.depth[k][(size_t)v * cam.width + u];
+            if (zb > 0.0f && d <= zb * factor) ++cnt;
+        }
+        if (!first) cnt += seen[i];
+        seen[i] = cnt;
+    }
+    if (n_any) {
+        const unsigned long long m = __ballot(cnt > 0);
+        if ((threadIdx.x & 63) == 0 && m) atomicAdd(n_any, (unsigned long long)__popcll(m));
+    }
+}
+
 struct Buf {
     void *p = nullptr;
     size_t bytes = 0;
@@ -373,6 +477,11 @@ struct apd_eval_ctx {
     Tree tree{};
     bool has_target = false;
     double build_ms = 0.0, query_ms = 0.0, voxel_ms = 0.0;
+    // render / visibility: the key plane of one view, staging for its outputs (render) or for the
+    // depth maps of one chunk of views (visibility), and the cloud's own bounds for the Morton order
+    Buf r_keys, r_depth, r_index, r_small;
+    bool render_morton = false;  // APD_EVAL_RENDER_ORDER=input|morton (input measured faster)
+    double render_ms = 0.0, visibility_ms = 0.0;
 };
 
 #define EV_OK(ctx, call)                                                                           \
@@ -453,6 +562,7 @@ apd_eval_ctx *apd_eval_create(int32_t device) {
     if (hipSetDevice(device) != hipSuccess) return nullptr;
     auto *ctx = new apd_eval_ctx();
     ctx->device = device;
+    if (const char *e = getenv("APD_EVAL_RENDER_ORDER")) ctx->render_morton = strcmp(e, "morton") == 0;
     if (hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking) != hipSuccess ||
         hipEventCreate(&ctx->ev0) != hipSuccess || hipEventCreate(&ctx->ev1) != hipSuccess) {
         apd_eval_destroy(ctx);
@@ -466,7 +576,7 @@ void apd_eval_destroy(apd_eval_ctx *ctx) {
     (void)hipSetDevice(ctx->device);
     for (Buf *b : {&ctx->t_xyz, &ctx->t_keys, &ctx->t_keys_s, &ctx->t_idx, &ctx->t_idx_s, &ctx->t_pts, &ctx->t_boxes,
                    &ctx->q_xyz, &ctx->q_keys, &ctx->q_keys_s, &ctx->q_idx, &ctx->q_idx_s, &ctx->q_dist, &ctx->q_aux,
-                   &ctx->sort_tmp, &ctx->small})
+                   &ctx->sort_tmp, &ctx->small, &ctx->r_keys, &ctx->r_depth, &ctx->r_index, &ctx->r_small})
         if (b->p) (void)hipFree(b->p);
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
     if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
@@ -708,6 +818,179 @@ int32_t apd_eval_get_timing(apd_eval_ctx *ctx, double *build_ms, double *query_m
     if (build_ms) *build_ms = ctx->build_ms;
     if (query_ms) *query_ms = ctx->query_ms;
     if (voxel_ms) *voxel_ms = ctx->voxel_ms;
+    return APD_OK;
+}
+
+static int check_views(apd_eval_ctx *ctx, const char *what, int32_t num_views, const apd_camera *cams) {
+    if (num_views < 0 || (num_views > 0 && !cams)) {
+        ctx->err = std::string(what) + ": bad view list";
+        return APD_EINVAL;
+    }
+    for (int v = 0; v < num_views; ++v)
+        if (cams[v].width < 1 || cams[v].height < 1 ||
+            (int64_t)cams[v].width * (int64_t)cams[v].height > ((int64_t)1 << 28)) {
+            ctx->err = std::string(what) + ": view " + std::to_string(v) + " has a size outside 1..2^28 pixels";
+            return APD_EINVAL;
+        }
+    return APD_OK;
+}
+
+int32_t apd_eval_render_depth(apd_eval_ctx *ctx, int64_t n64, const float *xyz, int32_t num_views,
+                              const apd_camera *cams, int32_t splat, float *const *depth, int32_t *const *index) {
+    if (!ctx) return APD_EINVAL;
+    int st = check_n(ctx, "apd_eval_render_depth", n64, xyz);
+    if (st || (st = check_views(ctx, "apd_eval_render_depth", num_views, cams))) return st;
+    if (splat < 0 || splat > 16) {
+        ctx->err = "apd_eval_render_depth: splat outside 0..16";
+        return APD_EINVAL;
+    }
+    if (num_views > 0 && !depth) {
+        ctx->err = "apd_eval_render_depth: NULL depth map list";
+        return APD_EINVAL;
+    }
+    for (int v = 0; v < num_views; ++v)
+        if (!depth[v]) {
+            ctx->err = "apd_eval_render_depth: NULL depth map";
+            return APD_EINVAL;
+        }
+    ctx->render_ms = 0.0;
+    if (num_views == 0) return APD_OK;
+    EV_OK(ctx, hipSetDevice(ctx->device));
+    const int n = (int)n64;
+    size_t max_pix = 0;
+    bool any_index = false;
+    for (int v = 0; v < num_views; ++v) {
+        max_pix = std::max(max_pix, (size_t)cams[v].width * (size_t)cams[v].height);
+        any_index = any_index || (index && index[v]);
+    }
+    if ((st = grow(ctx, ctx->r_keys, max_pix * 8)) || (st = grow(ctx, ctx->r_depth, max_pix * 4)) ||
+        (any_index && (st = grow(ctx, ctx->r_index, max_pix * 4))))
+        return st;
+    hipStream_t s = ctx->stream;
+    const int *order = nullptr;
+    double ms = 0.0, total = 0.0;
+    if (n > 0) {
+        if ((st = grow(ctx, ctx->q_xyz, (size_t)n * 12))) return st;
+        EV_OK(ctx, hipMemcpyAsync(ctx->q_xyz.p, xyz, (size_t)n * 12, hipMemcpyDefault, s));
+        if (ctx->render_morton) {
+            // the key-and-sort path of set_target over the cloud's own box; `small` keeps the target's
+            if ((st = grow(ctx, ctx->q_keys, (size_t)n * 8)) || (st = grow(ctx, ctx->q_keys_s, (size_t)n * 8)) ||
+                (st = grow(ctx, ctx->q_idx, (size_t)n * 4)) || (st = grow(ctx, ctx->q_idx_s, (size_t)n * 4)) ||
+                (st = grow(ctx, ctx->r_small, 64)))
+                return st;
+            uint32_t *bounds = (uint32_t *)ctx->r_small.p;
+            EV_OK(ctx, hipEventRecord(ctx->ev0, s));
+            EV_OK(ctx, hipMemsetAsync(bounds, 0xFF, 12, s));
+            EV_OK(ctx, hipMemsetAsync(bounds + 3, 0, 12, s));
+            hipLaunchKernelGGL(k_bounds, dim3(grid_capped(n)), dim3(BLOCK), 0, s, (const float *)ctx->q_xyz.p, n, bounds);
+            hipLaunchKernelGGL(k_morton_keys, dim3(grid_for(n)), dim3(BLOCK), 0, s, (const float *)ctx->q_xyz.p, n,
+                               (const uint32_t *)bounds, (uint64_t *)ctx->q_keys.p, (int *)ctx->q_idx.p,
+                               (unsigned long long *)nullptr);
+            EV_OK(ctx, hipGetLastError());
+            if ((st = sort_pairs(ctx, ctx->q_keys, ctx->q_keys_s, ctx->q_idx, ctx->q_idx_s, n))) return st;
+            EV_OK(ctx, hipEventRecord(ctx->ev1, s));
+            EV_OK(ctx, hipStreamSynchronize(s));
+            if ((st = elapsed(ctx, ms))) return st;
+            total += ms;
+            order = (const int *)ctx->q_idx_s.p;
+        }
+    }
+    for (int v = 0; v < num_views; ++v) {
+        const int npix = cams[v].width * cams[v].height;
+        int *idx_out = (index && index[v]) ? (int *)ctx->r_index.p : nullptr;
+        EV_OK(ctx, hipEventRecord(ctx->ev0, s));
+        EV_OK(ctx, hipMemsetAsync(ctx->r_keys.p, 0xFF, (size_t)npix * 8, s));
+        if (n > 0)
+            hipLaunchKernelGGL(k_splat, dim3(grid_for(n)), dim3(BLOCK), 0, s, (const float *)ctx->q_xyz.p, order, n,
+                               cams[v], (int)splat, (uint64_t *)ctx->r_keys.p);
+        hipLaunchKernelGGL(k_resolve, dim3(grid_for(npix)), dim3(BLOCK), 0, s, (const uint64_t *)ctx->r_keys.p, npix,
+                           (float *)ctx->r_depth.p, idx_out);
+        EV_OK(ctx, hipGetLastError());
+        EV_OK(ctx, hipEventRecord(ctx->ev1, s));
+        EV_OK(ctx, hipMemcpyAsync(depth[v], ctx->r_depth.p, (size_t)npix * 4, hipMemcpyDefault, s));
+        if (idx_out) EV_OK(ctx, hipMemcpyAsync(index[v], idx_out, (size_t)npix * 4, hipMemcpyDefault, s));
+        EV_OK(ctx, hipStreamSynchronize(s));
+        if ((st = elapsed(ctx, ms))) return st;
+        total += ms;
+    }
+    ctx->render_ms = total;
+    return APD_OK;
+}
+
+int32_t apd_eval_visibility(apd_eval_ctx *ctx, int64_t n64, const float *xyz, int32_t num_views,
+                            const apd_camera *cams, const float *const *depth, float rel_tol, int32_t *seen,
+                            int64_t *n_visible_any) {
+    if (!ctx) return APD_EINVAL;
+    int st = check_n(ctx, "apd_eval_visibility", n64, xyz);
+    if (st || (st = check_views(ctx, "apd_eval_visibility", num_views, cams))) return st;
+    if (!(rel_tol >= 0.0f) || !std::isfinite(rel_tol)) {
+        ctx->err = "apd_eval_visibility: rel_tol is negative or not finite";
+        return APD_EINVAL;
+    }
+    if ((n64 > 0 && !seen) || (num_views > 0 && !depth)) {
+        ctx->err = "apd_eval_visibility: NULL seen array or depth map list";
+        return APD_EINVAL;
+    }
+    for (int v = 0; v < num_views; ++v)
+        if (!depth[v]) {
+            ctx->err = "apd_eval_visibility: NULL depth map";
+            return APD_EINVAL;
+        }
+    EV_OK(ctx, hipSetDevice(ctx->device));
+    const int n = (int)n64;
+    ctx->visibility_ms = 0.0;
+    unsigned long long any = 0;
+    if (n == 0) {
+        if (n_visible_any) EV_OK(ctx, hipMemcpy(n_visible_any, &any, 8, hipMemcpyDefault));
+        return APD_OK;
+    }
+    if ((st = grow(ctx, ctx->q_xyz, (size_t)n * 12)) || (st = grow(ctx, ctx->q_dist, (size_t)n * 4)) ||
+        (st = grow(ctx, ctx->r_small, 64)))
+        return st;
+    hipStream_t s = ctx->stream;
+    int *d_seen = (int *)ctx->q_dist.p;
+    unsigned long long *counter = (unsigned long long *)((char *)ctx->r_small.p + 32);
+    EV_OK(ctx, hipMemcpyAsync(ctx->q_xyz.p, xyz, (size_t)n * 12, hipMemcpyDefault, s));
+    EV_OK(ctx, hipMemsetAsync(counter, 0, 8, s));
+    if (num_views == 0) EV_OK(ctx, hipMemsetAsync(d_seen, 0, (size_t)n * 4, s));
+    const float factor = 1.0f + rel_tol;  // one fp32 addition, made once
+    double ms = 0.0, total = 0.0;
+    for (int v0 = 0; v0 < num_views; v0 += VIS_CHUNK) {
+        VisViews vv{};
+        vv.n = std::min(VIS_CHUNK, num_views - v0);
+        size_t bytes = 0;
+        for (int k = 0; k < vv.n; ++k) bytes += (size_t)cams[v0 + k].width * (size_t)cams[v0 + k].height * 4;
+        if ((st = grow(ctx, ctx->r_depth, bytes))) return st;
+        size_t off = 0;
+        for (int k = 0; k < vv.n; ++k) {
+            const size_t b = (size_t)cams[v0 + k].width * (size_t)cams[v0 + k].height * 4;
+            vv.cam[k] = cams[v0 + k];
+            vv.depth[k] = (const float *)((char *)ctx->r_depth.p + off);
+            EV_OK(ctx, hipMemcpyAsync((char *)ctx->r_depth.p + off, depth[v0 + k], b, hipMemcpyDefault, s));
+            off += b;
+        }
+        const bool last = v0 + VIS_CHUNK >= num_views;
+        EV_OK(ctx, hipEventRecord(ctx->ev0, s));
+        hipLaunchKernelGGL(k_visibility, dim3(grid_for(n)), dim3(BLOCK), 0, s, (const float *)ctx->q_xyz.p, n, vv, factor,
+                           v0 == 0 ? 1 : 0, d_seen, last ? counter : (unsigned long long *)nullptr);
+        EV_OK(ctx, hipGetLastError());
+        EV_OK(ctx, hipEventRecord(ctx->ev1, s));
+        EV_OK(ctx, hipStreamSynchronize(s));  // the next chunk reuses the staging buffer and the events
+        if ((st = elapsed(ctx, ms))) return st;
+        total += ms;
+    }
+    EV_OK(ctx, hipMemcpyAsync(seen, d_seen, (size_t)n * 4, hipMemcpyDefault, s));
+    EV_OK(ctx, hipMemcpyAsync(&any, counter, 8, hipMemcpyDeviceToHost, s));
+    EV_OK(ctx, hipStreamSynchronize(s));
+    if (n_visible_any) EV_OK(ctx, hipMemcpy(n_visible_any, &any, 8, hipMemcpyDefault));
+    ctx->visibility_ms = total;
+    return APD_OK;
+}
+
+int32_t apd_eval_get_render_timing(apd_eval_ctx *ctx, double *render_ms, double *visibility_ms) {
+    if (!ctx) return APD_EINVAL;
+    if (render_ms) *render_ms = ctx->render_ms;
+    if (visibility_ms) *visibility_ms = ctx->visibility_ms;
     return APD_OK;
 }
 

@@ -2,7 +2,9 @@
 // cloud (cloud mode, on the GPU through include/apd_eval.h) and agreement of two sets of depth maps
 // (depth mode, host only). It stands where the reference calls an external evaluator
 // (tools/eval_eth_train.py), with the plain nearest-neighbour definition: the ETH3D tool's
-// free-space and visibility handling is not modelled.
+// free-space and visibility handling is not modelled. A ground-truth cloud can be rendered into the
+// scan's cameras with a z-buffer (render mode, and --gt_cloud in depth mode), and cloud mode can
+// restrict completeness to the ground-truth points such a z-buffer test sees (--visible_views).
 #include <algorithm>
 #include <atomic>
 #include <cmath>
@@ -16,6 +18,7 @@
 #include <vector>
 
 #include "../../include/apd_eval.h"
+#include "image.h"
 #include "io.h"
 
 using namespace apdhost;
@@ -28,6 +31,7 @@ const char *kHelp =
     "cloud mode (uses the GPU):\n"
     "  apd_eval --cloud REC.ply --gt GT.ply [--tolerances 0.01,0.02,0.05,0.1,0.2,0.5] [--max_dist D]\n"
     "           [--voxel V] [--gpu_index G] [--json OUT.json]\n"
+    "           [--scan S --visible_views K [--splat s] [--occlusion_tol r]]\n"
     "  R and G are the two clouds after dropping non-finite points and, for V > 0, keeping the\n"
     "  lowest-index point of every V-sized voxel of each cloud. Per tolerance t:\n"
     "    accuracy = #{dist(R_i, G) <= t} / |R|, completeness = #{dist(G_j, R) <= t} / |G|,\n"
@@ -36,20 +40,39 @@ const char *kHelp =
     "  tolerance). This is the DTU-style definition: the ETH3D evaluation's free-space and\n"
     "  visibility handling is NOT modelled, so the numbers compare runs of this project with each\n"
     "  other, not with published ETH3D tables.\n"
+    "  With --scan S --visible_views K (K >= 1) completeness is taken over G', the points of G seen\n"
+    "  in at least K of the reference views of S/pair.txt: G is rendered into every view with a\n"
+    "  z-buffer (footprint 2s+1 pixels, --splat s, default 0) and a point is seen in a view when it\n"
+    "  projects into the image no deeper than (1 + r) times the rendered depth at that pixel\n"
+    "  (--occlusion_tol r, default 0.01). Accuracy is still taken against all of G. This visibility\n"
+    "  filter is a z-buffer test, NOT ETH3D's free-space model.\n"
     "\n"
-    "depth mode (host only):\n"
-    "  apd_eval --dense_folder A (--against B | --gt_depth DIR) [--json OUT.json]\n"
+    "depth mode (host only, except --gt_cloud, which renders on the GPU):\n"
+    "  apd_eval --dense_folder A (--against B | --gt_depth DIR | --gt_cloud GT.ply [--splat s])\n"
+    "           [--json OUT.json]\n"
     "  For every reference view of A/pair.txt compares A/APD/<id>/depths.bin + weak.bin with\n"
-    "  B/APD/<id>/depths.bin + weak.bin, or with DIR/<id>.bin (CV_32FC1, valid where depth > 0).\n"
+    "  B/APD/<id>/depths.bin + weak.bin, or with DIR/<id>.bin (CV_32FC1, valid where depth > 0), or\n"
+    "  with GT.ply rendered into A's views in memory (the maps --render_gt would write).\n"
     "  valid = depth > 0 and weak != UNKNOWN. Reports valid pixels per side and in both, pixels\n"
     "  whose validity agrees, and among pixels valid in both the counts with |da - db| <= 1e-3 db\n"
     "  and <= 1e-2 db and the lower median of |da - db| / db.\n"
     "\n"
-    "Both modes may be combined in one invocation; --json then holds both.\n"
+    "render mode (uses the GPU):\n"
+    "  apd_eval --render_gt GT.ply --scan S --out DIR [--splat s] [--gpu_index G] [--json OUT.json]\n"
+    "  For every reference view of S/pair.txt writes DIR/<id>.bin (CV_32FC1, 0 = no surface, the\n"
+    "  layout --gt_depth reads): the z-buffer of GT.ply in the camera S/cams/<id>_cam.txt, at the\n"
+    "  size of S/APD/<id>/depths.bin when that exists, else of the image, the intrinsics rescaled\n"
+    "  from the image's size as fusion does. Nearest point per pixel, ties to the lowest index.\n"
+    "\n"
+    "The modes may be combined in one invocation; --json then holds all of them.\n"
     "Exit status: 0 ok, 1 run-time failure, 2 bad arguments or unreadable input.\n";
 
 struct Options {
-    std::string cloud, gt, json, dense, against, gt_depth;
+    std::string cloud, gt, json, dense, against, gt_depth, gt_cloud, render_gt, scan, out;
+    int splat = 0;
+    bool splat_given = false, occlusion_given = false;
+    int visible_views = 0;  // 0: no visibility filter
+    float occlusion_tol = 0.01f;
     std::vector<float> tol = {0.01f, 0.02f, 0.05f, 0.1f, 0.2f, 0.5f};
     float max_dist = -1.0f;  // < 0: the largest tolerance
     float voxel = 0.0f;
@@ -60,6 +83,14 @@ bool parse_float(const std::string &s, float &v) {
     char *end = nullptr;
     v = std::strtof(s.c_str(), &end);
     return !s.empty() && end && *end == '\0';
+}
+
+bool parse_int(const std::string &s, int &v) {
+    char *end = nullptr;
+    const long l = std::strtol(s.c_str(), &end, 10);
+    if (s.empty() || !end || *end != '\0' || l < -1000000 || l > 1000000) return false;
+    v = (int)l;
+    return true;
 }
 
 std::string fmt_g(double v) {
@@ -85,6 +116,144 @@ template <class T, class F> std::string join(const std::vector<T> &v, F f, const
     return s;
 }
 
+// ---- scan views and rendering --------------------------------------------------------------------
+
+bool read_pair_ids(const std::string &dense, std::vector<int> &ids, std::string &err);
+
+struct ScanView {
+    int id = 0;
+    apd_camera cam{};  // width / height: the view's size; K rescaled to it
+};
+
+// rows and cols of a bin-mat file from its 16-byte header
+bool probe_binmat_size(const std::string &path, int &rows, int &cols) {
+    std::ifstream in(path, std::ios::binary);
+    int32_t h[4];
+    if (!in || !in.read(reinterpret_cast<char *>(h), sizeof h) || h[0] != 1) return false;
+    rows = h[1];
+    cols = h[2];
+    return true;
+}
+
+// The reference views of scan/pair.txt with their cameras. The view size is that of
+// scan/APD/<id>/depths.bin when it exists, else the image's; the intrinsics are rescaled from the
+// image's size as fusion.cpp::load_view does (RescaleImageAndCamera).
+bool load_scan_views(const std::string &scan, std::vector<ScanView> &views, std::string &err) {
+    std::vector<int> ids;
+    if (!read_pair_ids(scan, ids, err)) return false;
+    static const char *exts[] = {".jpg", ".png", ".jpeg", ".JPG", ".PNG", ".JPEG"};  // as read_pair_file
+    for (int id : ids) {
+        ScanView v;
+        v.id = id;
+        const std::string name = format_index(id), cam = scan + "/cams/" + name + "_cam.txt";
+        if (!read_camera(cam, v.cam)) { err = "cannot read " + cam; return false; }
+        std::string img;
+        for (const char *e : exts)
+            if (file_exists(scan + "/images/" + name + e)) { img = scan + "/images/" + name + e; break; }
+        Gray8 src;
+        if (img.empty()) { err = "can not find image: " + scan + "/images/" + name; return false; }
+        if (!read_gray8(img, src, err)) { err = img + ": " + err; return false; }
+        int W = src.width, H = src.height;
+        const std::string dep = scan + "/APD/" + name + "/depths.bin";
+        if (file_exists(dep) && !probe_binmat_size(dep, H, W)) { err = "cannot read " + dep; return false; }
+        if (W < 1 || H < 1 || src.width < 1 || src.height < 1 || (int64_t)W * H > ((int64_t)1 << 28)) {
+            err = "view " + name + ": unusable size " + std::to_string(W) + "x" + std::to_string(H);
+            return false;
+        }
+        if (src.width != W || src.height != H) {
+            const float scale_x = W / static_cast<float>(src.width);
+            const float scale_y = H / static_cast<float>(src.height);
+            v.cam.K[0] *= scale_x;
+            v.cam.K[2] *= scale_x;
+            v.cam.K[4] *= scale_y;
+            v.cam.K[5] *= scale_y;
+        }
+        v.cam.width = W;
+        v.cam.height = H;
+        views.push_back(v);
+    }
+    return true;
+}
+
+constexpr size_t kViewBatch = 8;  // views rendered per library call (the cloud is uploaded once per call)
+
+// z-buffers of views [lo, hi) as CV_32FC1 Mats
+bool render_batch(apd_eval_ctx *ctx, const std::vector<float> &xyz, const std::vector<ScanView> &views, size_t lo,
+                  size_t hi, int splat, std::vector<Mat> &maps, double &render_ms) {
+    std::vector<apd_camera> cams;
+    std::vector<float *> ptrs;
+    maps.clear();
+    for (size_t i = lo; i < hi; ++i) {
+        cams.push_back(views[i].cam);
+        maps.emplace_back(views[i].cam.height, views[i].cam.width, (int)CV_32FC1);
+        ptrs.push_back(maps.back().ptr<float>());
+    }
+    const int st = apd_eval_render_depth(ctx, (int64_t)(xyz.size() / 3), xyz.data(), (int32_t)cams.size(), cams.data(),
+                                         splat, ptrs.data(), nullptr);
+    if (st != APD_OK) {
+        std::fprintf(stderr, "apd_eval: apd_eval_render_depth failed (%d): %s\n", st, apd_eval_last_error(ctx));
+        return false;
+    }
+    double ms = 0.0;
+    apd_eval_get_render_timing(ctx, &ms, nullptr);
+    render_ms += ms;
+    return true;
+}
+
+std::string esc(std::string s) {
+    for (char &ch : s)
+        if (ch == '"' || ch == '\\' || (unsigned char)ch < 32) ch = '\'';
+    return s;
+}
+
+struct RenderInputs {
+    std::vector<float> xyz;
+    std::vector<ScanView> views;
+};
+
+// returns the exit status; appends "render": {...} to json
+int run_render(const Options &opt, const RenderInputs &in, std::string &json) {
+    if (!make_dir(opt.out)) {
+        std::fprintf(stderr, "apd_eval: cannot create %s\n", opt.out.c_str());
+        return 1;
+    }
+    apd_eval_ctx *ctx = apd_eval_create(opt.gpu);
+    if (!ctx) {
+        std::fprintf(stderr, "apd_eval: %s (device %d)\n", apd_eval_last_error(nullptr), opt.gpu);
+        return 1;
+    }
+    double render_ms = 0.0;
+    std::vector<std::string> rows;
+    bool ok = true;
+    for (size_t lo = 0; ok && lo < in.views.size(); lo += kViewBatch) {
+        const size_t hi = std::min(in.views.size(), lo + kViewBatch);
+        std::vector<Mat> maps;
+        ok = render_batch(ctx, in.xyz, in.views, lo, hi, opt.splat, maps, render_ms);
+        for (size_t i = lo; ok && i < hi; ++i) {
+            const Mat &m = maps[i - lo];
+            const std::string path = opt.out + "/" + format_index(in.views[i].id) + ".bin";
+            if (!write_binmat_file(path, m)) {
+                std::fprintf(stderr, "apd_eval: cannot write %s\n", path.c_str());
+                ok = false;
+                break;
+            }
+            int64_t covered = 0;
+            const float *p = m.ptr<float>();
+            for (size_t k = 0, n = (size_t)m.rows * m.cols; k < n; ++k) covered += p[k] > 0.0f;
+            std::printf("rendered view %d: %dx%d covered %lld\n", in.views[i].id, m.cols, m.rows, (long long)covered);
+            rows.push_back("{\"id\": " + std::to_string(in.views[i].id) + ", \"width\": " + std::to_string(m.cols) +
+                           ", \"height\": " + std::to_string(m.rows) + ", \"covered\": " + std::to_string(covered) + "}");
+        }
+    }
+    apd_eval_destroy(ctx);
+    if (!ok) return 1;
+    json += "\"render\": {\"gt\": \"" + esc(opt.render_gt) + "\", \"scan\": \"" + esc(opt.scan) + "\", \"out\": \"" +
+            esc(opt.out) + "\", \"splat\": " + std::to_string(opt.splat) + ", \"points\": " +
+            std::to_string(in.xyz.size() / 3) + ", \"views\": [" +
+            join(rows, [](const std::string &r) { return r; }) + "], \"render_ms\": " + fmt_g(render_ms) + "}";
+    return 0;
+}
+
 // ---- cloud mode ---------------------------------------------------------------------------------
 
 struct Direction {
@@ -96,6 +265,7 @@ struct Direction {
 struct CloudInfo {
     std::vector<float> xyz;
     int64_t points_in = 0, points_finite = 0, points = 0;
+    int64_t points_visible = -1;  // |G'| with --visible_views, else unused
 };
 
 void drop_non_finite(CloudInfo &c) {
@@ -155,7 +325,39 @@ bool direction(apd_eval_ctx *ctx, const CloudInfo &q, const CloudInfo &t, const 
 
 std::string json_cloud(const CloudInfo &c) {
     return "{\"points_in\": " + std::to_string(c.points_in) + ", \"points_finite\": " + std::to_string(c.points_finite) +
-           ", \"points\": " + std::to_string(c.points) + "}";
+           ", \"points\": " + std::to_string(c.points) +
+           (c.points_visible >= 0 ? ", \"points_visible\": " + std::to_string(c.points_visible) : std::string()) + "}";
+}
+
+// G' = the points of g seen in at least opt.visible_views of the views: g is rendered into every
+// view and tested against its own z-buffers (a z-buffer test, not a free-space model)
+bool visible_subset(apd_eval_ctx *ctx, const CloudInfo &g, const std::vector<ScanView> &views, const Options &opt,
+                    CloudInfo &vis, double &render_ms, double &visibility_ms) {
+    std::vector<int32_t> seen((size_t)g.points, 0), part((size_t)g.points);
+    for (size_t lo = 0; lo < views.size(); lo += kViewBatch) {
+        const size_t hi = std::min(views.size(), lo + kViewBatch);
+        std::vector<Mat> maps;
+        if (!render_batch(ctx, g.xyz, views, lo, hi, opt.splat, maps, render_ms)) return false;
+        std::vector<apd_camera> cams;
+        std::vector<const float *> ptrs;
+        for (size_t i = lo; i < hi; ++i) {
+            cams.push_back(views[i].cam);
+            ptrs.push_back(maps[i - lo].ptr<float>());
+        }
+        const int st = apd_eval_visibility(ctx, g.points, g.xyz.data(), (int32_t)cams.size(), cams.data(), ptrs.data(),
+                                           opt.occlusion_tol, part.data(), nullptr);
+        if (st != APD_OK) return fail_ctx(ctx, "apd_eval_visibility", st);
+        double ms = 0.0;
+        apd_eval_get_render_timing(ctx, nullptr, &ms);
+        visibility_ms += ms;
+        for (size_t i = 0; i < seen.size(); ++i) seen[i] += part[i];
+    }
+    vis = CloudInfo{};
+    for (size_t i = 0; i < seen.size(); ++i)
+        if (seen[i] >= opt.visible_views)
+            for (int a = 0; a < 3; ++a) vis.xyz.push_back(g.xyz[3 * i + a]);
+    vis.points = (int64_t)(vis.xyz.size() / 3);
+    return true;
 }
 
 std::string json_direction(const Direction &d) {
@@ -166,15 +368,15 @@ std::string json_direction(const Direction &d) {
            fmt_g(d.build_ms) + ", \"query_ms\": " + fmt_g(d.query_ms) + "}";
 }
 
-// returns the exit status; appends "cloud": {...} to json
-int run_cloud(const Options &opt, std::string &json) {
+struct CloudInputs {
     CloudInfo rec, gt;
-    std::string err;
-    // both files are parsed before any device context exists: a malformed file fails without a GPU
-    if (!read_ply_xyz(opt.cloud, rec.xyz, err) || !read_ply_xyz(opt.gt, gt.xyz, err)) {
-        std::fprintf(stderr, "apd_eval: %s\n", err.c_str());
-        return 2;
-    }
+    std::vector<ScanView> views;  // with --visible_views
+};
+
+// returns the exit status; appends "cloud": {...} to json. The files were parsed by main() before
+// any device context existed: a malformed file fails without a GPU
+int run_cloud(const Options &opt, CloudInputs &in, std::string &json) {
+    CloudInfo &rec = in.rec, &gt = in.gt;
     drop_non_finite(rec);
     drop_non_finite(gt);
     const float max_dist = opt.max_dist >= 0.0f ? opt.max_dist : *std::max_element(opt.tol.begin(), opt.tol.end());
@@ -186,7 +388,15 @@ int run_cloud(const Options &opt, std::string &json) {
     Direction acc, comp;
     bool ok = true;
     if (opt.voxel > 0.0f) ok = downsample(ctx, rec, opt.voxel) && downsample(ctx, gt, opt.voxel);
-    ok = ok && direction(ctx, rec, gt, opt, max_dist, acc) && direction(ctx, gt, rec, opt, max_dist, comp);
+    const bool filter = opt.visible_views > 0;
+    CloudInfo gt_vis;
+    double render_ms = 0.0, visibility_ms = 0.0;
+    if (ok && filter) {
+        ok = visible_subset(ctx, gt, in.views, opt, gt_vis, render_ms, visibility_ms);
+        gt.points_visible = gt_vis.points;
+    }
+    ok = ok && direction(ctx, rec, gt, opt, max_dist, acc) &&
+         direction(ctx, filter ? gt_vis : gt, rec, opt, max_dist, comp);
     apd_eval_destroy(ctx);
     if (!ok) return 1;
 
@@ -202,11 +412,23 @@ int run_cloud(const Options &opt, std::string &json) {
         std::snprintf(b, sizeof b, "%.6f", v);
         return std::string(b);
     };
+    if (filter)
+        std::printf("Visible ground truth: %lld of %lld points (seen in >= %d of %zu views)\n",
+                    (long long)gt.points_visible, (long long)gt.points, opt.visible_views, in.views.size());
     std::printf("Tolerances: %s\n", join(opt.tol, fmt_f32, " ").c_str());
     std::printf("Completenesses: %s\n", join(c, six, " ").c_str());
     std::printf("Accuracies: %s\n", join(a, six, " ").c_str());
     std::printf("F1-scores: %s\n", join(f, six, " ").c_str());
-    json += "\"cloud\": {\"definition\": \"plain nearest neighbour (no free-space / visibility model)\", "
+    json += std::string("\"cloud\": {\"definition\": \"") +
+            (filter ? "plain nearest neighbour; completeness over the ground-truth points that pass a z-buffer "
+                      "visibility test (not the ETH3D free-space model)"
+                    : "plain nearest neighbour (no free-space / visibility model)") +
+            "\", " +
+            (filter ? "\"visibility\": {\"scan\": \"" + esc(opt.scan) + "\", \"views\": " + std::to_string(in.views.size()) +
+                          ", \"min_views\": " + std::to_string(opt.visible_views) + ", \"splat\": " +
+                          std::to_string(opt.splat) + ", \"occlusion_tol\": " + fmt_f32(opt.occlusion_tol) +
+                          ", \"render_ms\": " + fmt_g(render_ms) + ", \"visibility_ms\": " + fmt_g(visibility_ms) + "}, "
+                    : std::string()) +
             "\"tolerances\": [" + join(opt.tol, fmt_f32) + "], \"max_dist\": " +
             fmt_g((double)max_dist) + ", \"voxel\": " + fmt_g((double)opt.voxel) + ", \"rec\": " + json_cloud(rec) +
             ", \"gt\": " + json_cloud(gt) + ", \"accuracy\": " + json_direction(acc) + ", \"completeness\": " +
@@ -251,7 +473,8 @@ bool read_pair_ids(const std::string &dense, std::vector<int> &ids, std::string 
     return true;
 }
 
-void depth_view(const Options &opt, DepthStats &s) {
+// rendered: the ground-truth map of this view from --gt_cloud, else nullptr
+void depth_view(const Options &opt, DepthStats &s, const Mat *rendered) {
     const std::string name = format_index(s.id);
     Mat da, wa, db, wb;
     const std::string fa = opt.dense + "/APD/" + name;
@@ -259,8 +482,10 @@ void depth_view(const Options &opt, DepthStats &s) {
         s.error = "cannot read " + fa + "/depths.bin or weak.bin";
         return;
     }
-    const bool has_wb = opt.gt_depth.empty();
-    if (has_wb) {
+    const bool has_wb = !opt.against.empty();
+    if (rendered) {
+        db = *rendered;
+    } else if (has_wb) {
         const std::string fb = opt.against + "/APD/" + name;
         if (!read_binmat_file(fb + "/depths.bin", db) || !read_binmat_file(fb + "/weak.bin", wb)) {
             s.error = "cannot read " + fb + "/depths.bin or weak.bin";
@@ -317,24 +542,49 @@ std::string json_depth(const DepthStats &s, bool with_id) {
            ", \"within_1e-2\": " + std::to_string(s.within_1e2) + ", \"median_rel\": " + fmt_g(s.median_rel) + "}";
 }
 
-int run_depth(const Options &opt, std::string &json) {
+struct DepthInputs {
     std::vector<int> ids;
-    std::string err;
-    if (!read_pair_ids(opt.dense, ids, err)) {
-        std::fprintf(stderr, "apd_eval: %s\n", err.c_str());
-        return 2;
-    }
-    std::vector<DepthStats> views(ids.size());
-    for (size_t i = 0; i < ids.size(); ++i) views[i].id = ids[i];
-    std::atomic<size_t> next{0};
+    RenderInputs gt;  // with --gt_cloud: the cloud and A's views (ids in the same order)
+};
+
+// compares views [lo, hi); maps (may be empty) holds the rendered ground truth of those views
+void compare_views(const Options &opt, std::vector<DepthStats> &views, size_t lo, size_t hi,
+                   const std::vector<Mat> &maps) {
+    std::atomic<size_t> next{lo};
     const unsigned hw = std::thread::hardware_concurrency();
-    const size_t workers = std::max<size_t>(1, std::min<size_t>({(size_t)16, (size_t)(hw ? hw : 1), ids.size()}));
+    const size_t workers = std::max<size_t>(1, std::min<size_t>({(size_t)16, (size_t)(hw ? hw : 1), hi - lo}));
     std::vector<std::thread> pool;
     for (size_t w = 0; w < workers; ++w)
         pool.emplace_back([&] {
-            for (size_t i; (i = next.fetch_add(1)) < views.size();) depth_view(opt, views[i]);
+            for (size_t i; (i = next.fetch_add(1)) < hi;) depth_view(opt, views[i], maps.empty() ? nullptr : &maps[i - lo]);
         });
     for (auto &t : pool) t.join();
+}
+
+int run_depth(const Options &opt, const DepthInputs &in, std::string &json) {
+    const std::vector<int> &ids = in.ids;
+    std::vector<DepthStats> views(ids.size());
+    for (size_t i = 0; i < ids.size(); ++i) views[i].id = ids[i];
+    if (opt.gt_cloud.empty()) {
+        compare_views(opt, views, 0, views.size(), {});
+    } else {
+        apd_eval_ctx *ctx = apd_eval_create(opt.gpu);
+        if (!ctx) {
+            std::fprintf(stderr, "apd_eval: %s (device %d)\n", apd_eval_last_error(nullptr), opt.gpu);
+            return 1;
+        }
+        double render_ms = 0.0;
+        for (size_t lo = 0; lo < views.size(); lo += kViewBatch) {
+            const size_t hi = std::min(views.size(), lo + kViewBatch);
+            std::vector<Mat> maps;
+            if (!render_batch(ctx, in.gt.xyz, in.gt.views, lo, hi, opt.splat, maps, render_ms)) {
+                apd_eval_destroy(ctx);
+                return 1;
+            }
+            compare_views(opt, views, lo, hi, maps);
+        }
+        apd_eval_destroy(ctx);
+    }
 
     DepthStats total;
     int failed = 0;
@@ -364,14 +614,9 @@ int run_depth(const Options &opt, std::string &json) {
                 (long long)total.pixels, (long long)total.valid_a, (long long)total.valid_b, (long long)total.valid_both,
                 (long long)total.mask_agree, (long long)total.within_1e3, (long long)total.within_1e2, total.median_rel,
                 failed);
-    auto esc = [](std::string s) {
-        for (char &ch : s)
-            if (ch == '"' || ch == '\\' || (unsigned char)ch < 32) ch = '\'';
-        return s;
-    };
     json += "\"depth\": {\"a\": \"" + esc(opt.dense) + "\", \"b\": \"" +
-            esc(opt.gt_depth.empty() ? opt.against : opt.gt_depth) + "\", \"b_is_gt_depth\": " +
-            (opt.gt_depth.empty() ? "false" : "true") + ", \"views\": [" +
+            esc(!opt.against.empty() ? opt.against : !opt.gt_depth.empty() ? opt.gt_depth : opt.gt_cloud) +
+            "\", \"b_is_gt_depth\": " + (opt.against.empty() ? "true" : "false") + ", \"views\": [" +
             join(views, [](const DepthStats &s) { return json_depth(s, true); }) + "], \"failed_views\": " +
             std::to_string(failed) + ", \"total\": " + json_depth(total, false) + "}";
     return failed ? 1 : 0;
@@ -399,8 +644,21 @@ int main(int argc, char **argv) {
         else if (a == "--dense_folder") opt.dense = v;
         else if (a == "--against") opt.against = v;
         else if (a == "--gt_depth") opt.gt_depth = v;
+        else if (a == "--gt_cloud") opt.gt_cloud = v;
+        else if (a == "--render_gt") opt.render_gt = v;
+        else if (a == "--scan") opt.scan = v;
+        else if (a == "--out") opt.out = v;
         else if (a == "--gpu_index") opt.gpu = std::atoi(v.c_str());
-        else if (a == "--max_dist") {
+        else if (a == "--splat") {
+            if (!parse_int(v, opt.splat) || opt.splat < 0 || opt.splat > 16) return bad("bad --splat " + v + " (0..16)");
+            opt.splat_given = true;
+        } else if (a == "--visible_views") {
+            if (!parse_int(v, opt.visible_views) || opt.visible_views < 1) return bad("bad --visible_views " + v);
+        } else if (a == "--occlusion_tol") {
+            if (!parse_float(v, opt.occlusion_tol) || !(opt.occlusion_tol >= 0.0f) || !std::isfinite(opt.occlusion_tol))
+                return bad("bad --occlusion_tol " + v);
+            opt.occlusion_given = true;
+        } else if (a == "--max_dist") {
             if (!parse_float(v, opt.max_dist) || !(opt.max_dist >= 0.0f)) return bad("bad --max_dist " + v);
         } else if (a == "--voxel") {
             if (!parse_float(v, opt.voxel) || !(opt.voxel >= 0.0f) || !std::isfinite(opt.voxel))
@@ -420,27 +678,71 @@ int main(int argc, char **argv) {
         }
     }
     const bool cloud_mode = !opt.cloud.empty() || !opt.gt.empty();
-    const bool depth_mode = !opt.dense.empty() || !opt.against.empty() || !opt.gt_depth.empty();
-    if (!cloud_mode && !depth_mode) return bad("nothing to do");
+    const bool depth_mode = !opt.dense.empty() || !opt.against.empty() || !opt.gt_depth.empty() || !opt.gt_cloud.empty();
+    const bool render_mode = !opt.render_gt.empty();
+    if (!cloud_mode && !depth_mode && !render_mode) return bad("nothing to do");
     if (cloud_mode && (opt.cloud.empty() || opt.gt.empty())) return bad("cloud mode needs --cloud and --gt");
-    if (depth_mode && (opt.dense.empty() || opt.against.empty() == opt.gt_depth.empty()))
-        return bad("depth mode needs --dense_folder and exactly one of --against / --gt_depth");
+    if (depth_mode && (opt.dense.empty() ||
+                       (int)!opt.against.empty() + (int)!opt.gt_depth.empty() + (int)!opt.gt_cloud.empty() != 1))
+        return bad("depth mode needs --dense_folder and exactly one of --against / --gt_depth / --gt_cloud");
+    if (render_mode && (opt.scan.empty() || opt.out.empty())) return bad("render mode needs --render_gt, --scan and --out");
+    if (!render_mode && !opt.out.empty()) return bad("--out without --render_gt");
+    if (opt.visible_views > 0 && (!cloud_mode || opt.scan.empty()))
+        return bad("--visible_views needs cloud mode and --scan");
+    if (!opt.scan.empty() && !render_mode && opt.visible_views == 0)
+        return bad("--scan with nothing that uses it (--render_gt or --visible_views)");
+    if (opt.splat_given && !render_mode && opt.visible_views == 0 && opt.gt_cloud.empty())
+        return bad("--splat with nothing that renders");
+    if (opt.occlusion_given && opt.visible_views == 0) return bad("--occlusion_tol without --visible_views");
     if (cloud_mode && opt.max_dist >= 0.0f)
         for (float t : opt.tol)
             if (t > opt.max_dist) return bad("a tolerance exceeds --max_dist");
 
-    std::string json = "{";
-    int status = 0;
+    // every input is read here, before any device context exists: an unreadable one exits 2 without a GPU
+    DepthInputs din;
+    CloudInputs cin;
+    RenderInputs rin;
+    std::string err;
+    auto unreadable = [&] {
+        std::fprintf(stderr, "apd_eval: %s\n", err.c_str());
+        return 2;
+    };
     if (depth_mode) {
-        status = run_depth(opt, json);
-        if (status == 2) return 2;
+        if (!read_pair_ids(opt.dense, din.ids, err)) return unreadable();
+        if (!opt.gt_cloud.empty() &&
+            (!read_ply_xyz(opt.gt_cloud, din.gt.xyz, err) || !load_scan_views(opt.dense, din.gt.views, err)))
+            return unreadable();
     }
     if (cloud_mode) {
-        if (depth_mode) json += ", ";
-        const int st = run_cloud(opt, json);
-        if (st == 2) return 2;
+        if (!read_ply_xyz(opt.cloud, cin.rec.xyz, err) || !read_ply_xyz(opt.gt, cin.gt.xyz, err)) return unreadable();
+        if (opt.visible_views > 0 && !load_scan_views(opt.scan, cin.views, err)) return unreadable();
+    }
+    if (render_mode && (!read_ply_xyz(opt.render_gt, rin.xyz, err) || !load_scan_views(opt.scan, rin.views, err)))
+        return unreadable();
+
+    std::string json = "{";
+    int status = 0;
+    bool first = true;
+    auto sep = [&] {
+        if (!first) json += ", ";
+        first = false;
+    };
+    if (depth_mode) {
+        sep();
+        status = run_depth(opt, din, json);
+        if (status != 0 && json.size() == 1) json += "\"depth\": null";
+    }
+    if (cloud_mode) {
+        sep();
+        const int st = run_cloud(opt, cin, json);
         status = std::max(status, st);
         if (st != 0) json += "\"cloud\": null";
+    }
+    if (render_mode) {
+        sep();
+        const int st = run_render(opt, rin, json);
+        status = std::max(status, st);
+        if (st != 0) json += "\"render\": null";
     }
     json += "}\n";
     if (!opt.json.empty()) {

@@ -5,7 +5,8 @@
  * (tools/eval_eth_train.py). This ABI computes the part of that which is heavy: for every point of
  * one cloud the distance to the nearest point of another, truncated at max_dist, plus a voxel
  * down-sampling of a cloud. It is the plain nearest-neighbour definition (DTU-style); the ETH3D
- * tool's free-space and visibility handling is not modelled.
+ * tool's free-space and visibility handling is not modelled. A z-buffer renderer of a cloud into
+ * cameras and a per-point visibility count against depth maps serve a plain visibility filter.
  *
  * Distance contract (bit for bit, all arithmetic fp32 and nothing contracted):
  *   - a target with a non-finite coordinate never matches; a query with one gives +inf
@@ -14,8 +15,30 @@
  *   - no finite target: every result is +inf
  *   - within[k] = #{i : dist_i <= tol[k]} (fp32 comparison, exact integer counts)
  *
+ * Render / visibility contract (bit for bit, all arithmetic fp32, nothing contracted, every sum
+ * evaluated left to right). Point i = (x, y, z) in the view of camera (K, R, t, width W, height H):
+ *   - projection, the project() statement of csrc/apd_fusion.hip (ProjectCamera):
+ *       tx = R0*x + R1*y + R2*z + t0;  ty = R3*x + R4*y + R5*z + t1;  tz = R6*x + R7*y + R8*z + t2
+ *       d  = K6*tx + K7*ty + K8*tz
+ *       px = (K0*tx + K1*ty + K2*tz) / d;  py = (K3*tx + K4*ty + K5*tz) / d
+ *   - the point is dropped (takes no part in the view) if a coordinate is non-finite, or unless
+ *     d > 0 and d < +inf
+ *   - u = trunc_x86(px + 0.5f), v = trunc_x86(py + 0.5f): truncation, INT32_MIN for NaN and for
+ *     values outside the int range (fusion's trunc_x86)
+ *   - render: the point covers the pixels (a, b) with |a - u| <= splat and |b - v| <= splat that lie
+ *     inside the image (no integer overflow: u = INT32_MIN covers nothing; a centre just outside
+ *     still covers the part of its footprint that is inside). Every covered pixel receives the key
+ *     (bits(d) << 32) | i and keeps the minimum: the nearest depth, ties to the lowest point index.
+ *     depth[p] = the float in the high word, 0.0f if uncovered; index[p] = the low word, -1 if
+ *     uncovered. Integer atomics: the result does not depend on the order of arrival.
+ *   - visibility: point i is visible in view v iff it is not dropped, 0 <= u < W and 0 <= v < H (the
+ *     centre pixel only), zb = depth_v[v*W + u] > 0, and d <= zb * (1.0f + rel_tol), the factor
+ *     being one fp32 addition made once. A NaN zb compares false.
+ * This is a z-buffer test; it is still not the ETH3D tool's free-space model.
+ *
  * Conventions as in apd_fusion.h: plain C types, APD_OK or a negative apd_status, never exit().
- * Every data pointer (xyz, dist, tol, within, keep_idx, n_keep) may be a host or a device pointer.
+ * Every data pointer (xyz, dist, tol, within, keep_idx, n_keep, the depth and index maps, seen,
+ * n_visible_any) may be a host or a device pointer.
  * The calls work on the context's own stream and return after it has drained.
  *
  * These declarations are not part of apd_abi_version()'s export set (apd_hip.h + apd_fusion.h).
@@ -61,6 +84,31 @@ int32_t apd_eval_voxel_downsample(apd_eval_ctx *ctx, int64_t n, const float *xyz
 /* Device-event times of the last set_target / distances / voxel_downsample call, in ms (0 for a
    call that has not happened or launched nothing). Any pointer may be NULL. */
 int32_t apd_eval_get_timing(apd_eval_ctx *ctx, double *build_ms, double *query_ms, double *voxel_ms);
+
+/* z-buffer of a cloud in num_views cameras. cams[v].width/height give view v's size.
+   depth[v]: W*H floats, 0 where nothing projects. index[v]: W*H int32, -1 there.
+   index, or any index[v], may be NULL. xyz, depth[v], index[v] may be host or device
+   pointers; the pointer arrays and cams are host memory. The cloud is uploaded once per call.
+   The points are offered to the kernel in input order (default) or in the Morton order of the
+   cloud (environment APD_EVAL_RENDER_ORDER=input|morton, read by apd_eval_create); the output does
+   not depend on it.
+   APD_EINVAL: n out of range, xyz NULL with n > 0, num_views < 0, cams, depth or a depth[v] NULL
+   with num_views > 0, a view with width < 1, height < 1 or width*height > 2^28, splat outside 0..16. */
+int32_t apd_eval_render_depth(apd_eval_ctx *ctx, int64_t n, const float *xyz, int32_t num_views,
+                              const apd_camera *cams, int32_t splat,
+                              float *const *depth, int32_t *const *index);
+
+/* seen[i] = number of views in which point i is visible against depth[v] (any depth map of
+   that view's size: a rendered one or a reconstructed one). n_visible_any (may be NULL) =
+   #{i : seen[i] > 0}. xyz, depth[v], seen and n_visible_any may be host or device pointers.
+   APD_EINVAL: as above, seen NULL with n > 0, rel_tol negative or not finite. */
+int32_t apd_eval_visibility(apd_eval_ctx *ctx, int64_t n, const float *xyz, int32_t num_views,
+                            const apd_camera *cams, const float *const *depth, float rel_tol,
+                            int32_t *seen, int64_t *n_visible_any);
+
+/* Device-event times of the last render_depth (sort + per view: clear, splat, resolve) and
+   visibility (kernels only) call, in ms. Any pointer may be NULL. */
+int32_t apd_eval_get_render_timing(apd_eval_ctx *ctx, double *render_ms, double *visibility_ms);
 
 #ifdef __cplusplus
 }
