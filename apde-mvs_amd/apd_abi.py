@@ -232,7 +232,9 @@ EXPORTS = ["apd_abi_version", "apd_device_count", "apd_create", "apd_destroy", "
 # include/apd_eval.h: its own list (EXPORTS is the apd_hip.h + apd_fusion.h set apd_abi_version() covers)
 EVAL_EXPORTS = ["apd_eval_create", "apd_eval_destroy", "apd_eval_last_error", "apd_eval_set_target",
                 "apd_eval_distances", "apd_eval_voxel_downsample", "apd_eval_get_timing",
-                "apd_eval_render_depth", "apd_eval_visibility", "apd_eval_get_render_timing"]
+                "apd_eval_render_depth", "apd_eval_visibility", "apd_eval_get_render_timing",
+                "apd_eval_cube_cameras", "apd_eval_free_gap", "apd_eval_voxel_scores",
+                "apd_eval_get_protocol_timing"]
 
 
 def camera_from_values(v) -> ApdCamera:
@@ -360,6 +362,16 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
                                         C.POINTER(C.c_void_p), C.c_float, C.c_void_p, C.c_void_p]
     lib.apd_eval_get_render_timing.restype = C.c_int32
     lib.apd_eval_get_render_timing.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    lib.apd_eval_cube_cameras.restype = C.c_int32
+    lib.apd_eval_cube_cameras.argtypes = [C.c_void_p, C.c_int32, C.POINTER(ApdCamera)]
+    lib.apd_eval_free_gap.restype = C.c_int32
+    lib.apd_eval_free_gap.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.POINTER(ApdCamera),
+                                      C.POINTER(C.c_void_p), C.c_void_p]
+    lib.apd_eval_voxel_scores.restype = C.c_int32
+    lib.apd_eval_voxel_scores.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p,
+                                          C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.apd_eval_get_protocol_timing.restype = C.c_int32
+    lib.apd_eval_get_protocol_timing.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     return lib
 
 
@@ -424,9 +436,26 @@ class FusionEngine:
             pass
 
 
+ETH3D_TOLERANCES = (0.01, 0.02, 0.05, 0.1, 0.2, 0.5)  # the ones tools/eval_eth_train.py passes
+
+
+def cube_cameras(origin, size: int, lib: Optional[C.CDLL] = None):
+    """The six ApdCamera faces (+X, -X, +Y, -Y, +Z, -Z) of a cube map of size x size pixels centred at
+    origin (apd_eval_cube_cameras). Host only: needs no GPU."""
+    lib = lib or load_library()
+    o = np.ascontiguousarray(origin, np.float32).reshape(-1)
+    if len(o) != 3:
+        raise ValueError("origin is three floats")
+    arr = (ApdCamera * 6)()
+    st = lib.apd_eval_cube_cameras(o.ctypes.data, int(size), arr)
+    if st != 0:
+        raise ApdError(f"apd_eval_cube_cameras -> {STATUS.get(st, st)}: size outside 2..16384 or a non-finite origin")
+    return [arr[i] for i in range(6)]
+
+
 class EvalEngine:
-    """One apd_eval_ctx (include/apd_eval.h): truncated nearest-neighbour distances to a target cloud
-    and voxel down-sampling. Clouds are (n, 3) float32: numpy arrays (results come back as numpy) or
+    """One apd_eval_ctx (include/apd_eval.h): truncated nearest-neighbour distances to a target cloud,
+    voxel down-sampling, z-buffer rendering and visibility, free gaps and voxel scores. Clouds are (n, 3) float32: numpy arrays (results come back as numpy) or
     torch tensors on the context's device (results come back as tensors there; torch's current
     stream is waited for first, as for every device input of this library)."""
 
@@ -589,6 +618,74 @@ class EvalEngine:
                     "apd_eval_get_render_timing")
         return {"render_ms": r.value, "visibility_ms": v.value}
 
+    def free_gap_ptr(self, n: int, xyz_ptr, cams, depth_ptrs, gap_ptr):
+        arr = cams if isinstance(cams, C.Array) else self._cams(cams)
+        nv = len(depth_ptrs)
+        dp = (C.c_void_p * max(nv, 1))(*depth_ptrs)
+        self._check(self.lib.apd_eval_free_gap(self.ctx, n, xyz_ptr, nv, arr, dp, gap_ptr), "apd_eval_free_gap")
+
+    def free_gap(self, xyz, cams, depths):
+        """gap float32[n]: the largest `depth at the point's pixel - depth of the point` over the views
+        whose map covers the point's centre pixel (-inf without one): how far in front of the
+        surfaces of depths[v] (an (H, W) float32 map per camera, numpy or torch) the point lies."""
+        a, n, addr, dev = self._cloud(xyz)
+        arr = self._cams(cams)
+        if len(depths) != len(cams):
+            raise ValueError("one depth map per camera")
+        maps = [_keep(d, np.float32) for d in depths]
+        for i, m in enumerate(maps):
+            if tuple(m.shape) != (int(arr[i].height), int(arr[i].width)):
+                raise ValueError(f"depth map {i} has shape {tuple(m.shape)}, its camera {arr[i].height}x{arr[i].width}")
+        if dev:
+            import torch
+            gap = torch.empty(n, dtype=torch.float32, device=a.device)
+            gptr = gap.data_ptr() if n else None
+        else:
+            gap = np.empty(n, np.float32)
+            gptr = gap.ctypes.data if n else None
+        _torch_device_sync(a, gap, maps)
+        ptrs = [m.data_ptr() if hasattr(m, "data_ptr") else m.ctypes.data for m in maps]
+        self.free_gap_ptr(n, addr, arr, ptrs, gptr)
+        return gap
+
+    def voxel_scores_ptr(self, n: int, xyz_ptr, voxel: float, dist_ptr, gap_ptr, num_tol: int, tol_ptr, good_ptr,
+                         bad_ptr, ratio_sum_ptr, voxels_ptr):
+        self._check(self.lib.apd_eval_voxel_scores(self.ctx, n, xyz_ptr, voxel, dist_ptr, gap_ptr, num_tol, tol_ptr,
+                                                   good_ptr, bad_ptr, ratio_sum_ptr, voxels_ptr),
+                    "apd_eval_voxel_scores")
+
+    def voxel_scores(self, xyz, voxel: float, dist, gap=None, tolerances=ETH3D_TOLERANCES) -> dict:
+        """Per tolerance: good / bad point totals, the integer sum of the per-voxel fixed-point
+        ratios (a << 32) // (a + b) and the number of voxels with a + b > 0 (include/apd_eval.h),
+        as int64 arrays under "good", "bad", "ratio_sum", "voxels" (numpy, or tensors on the cloud's
+        device), plus "score": ratio_sum / (voxels * 2^32) as a list of floats, 0 without voxels."""
+        a, n, addr, dev = self._cloud(xyz)
+        d = _keep(dist, np.float32)
+        g = _keep(gap, np.float32)
+        for name, v in (("dist", d), ("gap", g)):
+            if v is not None and tuple(v.shape) != (n,):
+                raise ValueError(f"{name} has shape {tuple(v.shape)}, the cloud {n} points")
+        tol = np.ascontiguousarray(tolerances, np.float32).reshape(-1)
+        k = len(tol)
+        if dev:
+            import torch
+            outs = [torch.zeros(k, dtype=torch.int64, device=a.device) for _ in range(4)]
+        else:
+            outs = [np.zeros(k, np.int64) for _ in range(4)]
+        _torch_device_sync(a, d, g, outs)
+        ptr = lambda t: None if t is None or not len(t) else (t.data_ptr() if hasattr(t, "data_ptr") else t.ctypes.data)
+        self.voxel_scores_ptr(n, addr, voxel, ptr(d), ptr(g), k, ptr(tol), *[ptr(o) for o in outs])
+        res = dict(zip(("good", "bad", "ratio_sum", "voxels"), outs))
+        res["score"] = [float(int(r)) / (float(int(v)) * 4294967296.0) if int(v) else 0.0
+                        for r, v in zip(res["ratio_sum"].tolist(), res["voxels"].tolist())]
+        return res
+
+    def protocol_timing(self) -> dict:
+        f, s = C.c_double(), C.c_double()
+        self._check(self.lib.apd_eval_get_protocol_timing(self.ctx, C.byref(f), C.byref(s)),
+                    "apd_eval_get_protocol_timing")
+        return {"free_gap_ms": f.value, "scores_ms": s.value}
+
     def close(self):
         if self.ctx:
             self.lib.apd_eval_destroy(self.ctx)
@@ -599,9 +696,6 @@ class EvalEngine:
             self.close()
         except Exception:
             pass
-
-
-ETH3D_TOLERANCES = (0.01, 0.02, 0.05, 0.1, 0.2, 0.5)  # the ones tools/eval_eth_train.py passes
 
 
 def cloud_metrics(rec_xyz, gt_xyz, tolerances=ETH3D_TOLERANCES, max_dist=None, voxel: float = 0.0,
@@ -663,6 +757,82 @@ def cloud_metrics(rec_xyz, gt_xyz, tolerances=ETH3D_TOLERANCES, max_dist=None, v
             out["timing_ms"][name] = {"build_ms": tm["build_ms"], "query_ms": tm["query_ms"]}
         out["f1"] = [2 * a * c / (a + c) if a + c > 0 else 0.0
                      for a, c in zip(ratios["accuracy"], ratios["completeness"])]
+    finally:
+        if engine is None:
+            eng.close()
+    return out
+
+
+def cloud_metrics_scanners(rec_xyz, scans, tolerances=ETH3D_TOLERANCES, voxel: float = 0.01, cube_size: int = 2048,
+                           splat: int = 1, max_dist=None, engine: Optional[EvalEngine] = None) -> dict:
+    """Accuracy / completeness / F1 of a reconstructed cloud against laser scans with a scanner
+    free-space model and voxel-averaged scores, the `apd_eval --gt_mlp` mode's sequence of calls.
+    scans: a list of (points (n, 3) float32 in world coordinates, origin (3,)) per scanner position.
+
+    R = the finite points of rec_xyz, G = the finite points of all scans in order. No cloud is
+    down-sampled; `voxel` is the scoring voxel. Per tolerance t:
+      accuracy: a point of R is good iff dist(R_i, G) <= t; bad iff it is not good and lies more
+        than t in front of the surface some scanner saw along its ray (free_gap > t, the gap taken
+        against the cube-map z-buffers of every scanner, each rendered from that scanner's own
+        points with footprint `splat`); otherwise it is unobserved (behind the scanned surface, or
+        where no beam went) and does not count.
+      completeness: a point of G is good iff dist(G_j, R) <= t, else bad.
+      Each score is the mean over the voxels with a counted point of good / (good + bad), as the
+      fixed-point integers of include/apd_eval.h; F1 = 2ac / (a + c), 0 when a + c = 0.
+    Distances are truncated at max_dist (default: the largest tolerance).
+
+    Modelled on the ETH3D evaluation protocol but not the ETH3D tool: a z-buffer per cube-map pixel
+    instead of per-beam cones, a free-space margin equal to the tolerance, integer-rounded voxel
+    ratios. Parity with that tool is not pinned; the numbers are not for published tables."""
+    tol = np.ascontiguousarray(tolerances, np.float32).reshape(-1)
+    md = float(tol.max()) if max_dist is None else float(np.float32(max_dist))
+    eng = engine or EvalEngine()
+
+    def finite(x):
+        a = np.ascontiguousarray(x, np.float32).reshape(-1, 3)
+        return np.ascontiguousarray(a[np.isfinite(a).all(axis=1)])
+
+    out = {"tolerances": [float(t) for t in tol], "max_dist": md, "voxel": float(np.float32(voxel)),
+           "cube_size": int(cube_size), "splat": int(splat), "timing_ms": {}}
+    try:
+        R = finite(rec_xyz)
+        parts = [finite(p) for p, _ in scans]
+        origins = [np.ascontiguousarray(o, np.float32).reshape(3) for _, o in scans]
+        G = np.ascontiguousarray(np.concatenate(parts + [np.zeros((0, 3), np.float32)]))
+        out["rec"] = {"points": int(len(R))}
+        out["gt"] = {"points": int(len(G))}
+        out["scanners"] = [{"points": int(len(p)), "origin": [float(v) for v in o]} for p, o in zip(parts, origins)]
+
+        def side(name, q, t, gap):
+            eng.set_target(t)
+            dist, _ = eng.distances(q, md)
+            tm = eng.timing()
+            sc = eng.voxel_scores(q, voxel, dist, gap, tol)
+            good = [int(v) for v in sc["good"]]
+            bad = [int(v) for v in sc["bad"]]
+            out[name] = {"points": int(len(q)), "good": good, "bad": bad,
+                         "unobserved": [len(q) - g - b for g, b in zip(good, bad)],
+                         "ratio_sum": [int(v) for v in sc["ratio_sum"]], "voxels": [int(v) for v in sc["voxels"]],
+                         "score": sc["score"], "plain_of_all": [g / len(q) if len(q) else 0.0 for g in good],
+                         "plain": [g / (g + b) if g + b else 0.0 for g, b in zip(good, bad)]}
+            out["timing_ms"][name] = {"build_ms": tm["build_ms"], "query_ms": tm["query_ms"],
+                                      "scores_ms": eng.protocol_timing()["scores_ms"]}
+            return dist
+
+        gap = np.full(len(R), -np.inf, np.float32)
+        render_ms = gap_ms = 0.0
+        for p, o in zip(parts, origins):  # one scanner's six maps at a time
+            cams = cube_cameras(o, cube_size, eng.lib)
+            maps = eng.render_depth(p, cams, splat)
+            render_ms += eng.render_timing()["render_ms"]
+            gap = np.maximum(gap, eng.free_gap(R, cams, maps))
+            gap_ms += eng.protocol_timing()["free_gap_ms"]
+        out["timing_ms"]["free_space"] = {"render_ms": render_ms, "free_gap_ms": gap_ms}
+        out["accuracy_dist"] = side("accuracy", R, G, gap)
+        out["accuracy_gap"] = gap
+        out["completeness_dist"] = side("completeness", G, R, None)
+        out["f1"] = [2 * a * c / (a + c) if a + c > 0 else 0.0
+                     for a, c in zip(out["accuracy"]["score"], out["completeness"]["score"])]
     finally:
         if engine is None:
             eng.close()

@@ -1,6 +1,7 @@
 // apd_eval.hip — device side of the point-cloud evaluation (include/apd_eval.h): truncated
 // nearest-neighbour distances between two clouds, voxel down-sampling, and a z-buffer renderer of a
-// cloud into cameras with a per-point visibility count (integer atomics: deterministic).
+// cloud into cameras with a per-point visibility count (integer atomics: deterministic), the
+// free-space gap of points against depth maps and per-voxel good / bad scores (integer sums).
 //
 // Search structure: a Morton-sorted implicit bounding-volume tree.
 //   - finite targets are quantised to 21 bits per axis over their bounding box (in double) and sorted
@@ -15,6 +16,9 @@
 #include <hip/hip_runtime.h>
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
+#include <rocprim/device/device_scan_by_key.hpp>
+#include <rocprim/iterator/counting_iterator.hpp>
+#include <rocprim/iterator/transform_iterator.hpp>
 
 #include <cmath>
 #include <cstdint>
@@ -454,6 +458,84 @@ __global__ void __launch_bounds__(BLOCK) k_visibility(const float *__restrict__ 
     }
 }
 
+// One lane per point, the views of k_visibility. gap = max over the views that cover the point's
+// centre pixel with zb > 0 of zb - d (one fp32 subtraction, never NaN: zb > 0 rules a NaN zb out and
+// d is finite), -inf without such a view. first: this launch starts the maximum, otherwise it goes
+// on from the earlier chunks'. The maximum does not depend on the order of the views.
+__global__ void __launch_bounds__(BLOCK) k_free_gap(const float *__restrict__ xyz, int n, const VisViews vv, int first,
+                                                    float *gap) {
+    const int i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const float x = xyz[3 * (size_t)i], y = xyz[3 * (size_t)i + 1], z = xyz[3 * (size_t)i + 2];
+    float g = first ? __uint_as_float(0xFF800000u) : gap[i];
+    for (int k = 0; k < vv.n; ++k) {
+        const apd_camera &cam = vv.cam[k];
+        float d;
+        int u, v;
+        if (!project_point(cam, x, y, z, d, u, v)) continue;
+        if (u < 0 || u >= cam.width || v < 0 || v >= cam.height) continue;
+        const float zb = vv.depth[k][(size_t)v * cam.width + u];
+        if (zb > 0.0f) {
+            const float e = zb - d;
+            if (e > g) g = e;
+        }
+    }
+    gap[i] = g;
+}
+
+// ---- voxel scores ---------------------------------------------------------------------------------
+
+// The class of the point at sorted position i for one tolerance, as the summand of the per-voxel
+// scan: good << 32 | bad (a run holds fewer than 2^31 points, so neither half carries).
+// good: dist <= tol. bad: not good and (no gap given or gap > tol). NaN compares false.
+struct ClassOf {
+    const int *idx;
+    const float *dist;
+    const float *gap;  // may be nullptr
+    float tol;
+    __device__ __forceinline__ uint64_t operator()(int i) const {
+        const int j = idx[i];
+        const bool good = dist[j] <= tol;
+        const bool bad = !good && (gap == nullptr || gap[j] > tol);
+        return (uint64_t)good << 32 | (uint64_t)bad;
+    }
+};
+
+// cnt = the inclusive scan of ClassOf within every run of equal keys, so the last entry of a run
+// holds the voxel's (a << 32 | b). Grid-stride over the sorted positions; per lane, then per wave,
+// integer sums of a, b, the fixed-point ratio (a << 32) / (a + b) and the number of voxels with
+// a + b > 0; the waves of a block meet in LDS, then one integer atomic per block and output (every
+// block adds to the same four words, so the atomics are kept few: RATIO_GRID blocks at the most).
+// out: good, bad, ratio_sum, voxels.
+constexpr int RATIO_GRID = 1024;
+__global__ void __launch_bounds__(BLOCK) k_voxel_ratio(const uint64_t *__restrict__ keys,
+                                                       const uint64_t *__restrict__ cnt, int n,
+                                                       unsigned long long *out) {
+    __shared__ unsigned long long part[BLOCK / 64][4];
+    unsigned long long acc[4] = {0ull, 0ull, 0ull, 0ull};
+    for (int i = blockIdx.x * BLOCK + threadIdx.x; i < n; i += gridDim.x * BLOCK) {
+        const uint64_t k = keys[i];
+        if (k == KEY_NONE || (i + 1 < n && keys[i + 1] == k)) continue;
+        const uint64_t c = cnt[i], a = c >> 32, b = c & 0xFFFFFFFFull;
+        if (a + b == 0) continue;
+        acc[0] += a;
+        acc[1] += b;
+        acc[2] += (a << 32) / (a + b);
+        acc[3] += 1;
+    }
+    for (int q = 0; q < 4; ++q) {
+        unsigned long long v = acc[q];
+        for (int s = 32; s > 0; s >>= 1) v += __shfl_xor(v, s);
+        if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6][q] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x < 4) {
+        unsigned long long v = 0;
+        for (int w = 0; w < BLOCK / 64; ++w) v += part[w][threadIdx.x];
+        if (v) atomicAdd(&out[threadIdx.x], v);
+    }
+}
+
 struct Buf {
     void *p = nullptr;
     size_t bytes = 0;
@@ -482,6 +564,10 @@ struct apd_eval_ctx {
     Buf r_keys, r_depth, r_index, r_small;
     bool render_morton = false;  // APD_EVAL_RENDER_ORDER=input|morton (input measured faster)
     double render_ms = 0.0, visibility_ms = 0.0;
+    // free gap / voxel scores: device copies of dist and gap, the per-run scan of one tolerance and
+    // the four sums of every tolerance
+    Buf s_dist, s_gap, s_cnt, s_out;
+    double free_gap_ms = 0.0, scores_ms = 0.0;
 };
 
 #define EV_OK(ctx, call)                                                                           \
@@ -554,6 +640,44 @@ static float d2_bound(float md) {
     return b;
 }
 
+// The voxel keys of the n points in q_xyz, sorted: q_keys_s / q_idx_s (stable, so equal keys keep
+// ascending input indices; non-finite points sort last under KEY_NONE). bounds: 6 words of device
+// scratch. none = true (and nothing sorted) when no point is finite. Drains the stream once.
+static int voxel_sorted_keys(apd_eval_ctx *ctx, const char *what, int n, float voxel, uint32_t *bounds, bool &none) {
+    hipStream_t s = ctx->stream;
+    int st;
+    EV_OK(ctx, hipMemsetAsync(bounds, 0xFF, 12, s));
+    EV_OK(ctx, hipMemsetAsync(bounds + 3, 0, 12, s));
+    hipLaunchKernelGGL(k_voxel_bounds, dim3(grid_capped(n)), dim3(BLOCK), 0, s, (const float *)ctx->q_xyz.p, n, voxel,
+                       bounds);
+    EV_OK(ctx, hipGetLastError());
+    uint32_t hb[6];
+    EV_OK(ctx, hipMemcpyAsync(hb, bounds, 24, hipMemcpyDeviceToHost, s));
+    EV_OK(ctx, hipStreamSynchronize(s));
+    none = hb[0] == 0xFFFFFFFFu;
+    if (none) return APD_OK;
+    float mn[3];
+    for (int a = 0; a < 3; ++a) {
+        auto dec = [](uint32_t u) {
+            const uint32_t b = (u & 0x80000000u) ? (u & 0x7FFFFFFFu) : ~u;
+            float f;
+            memcpy(&f, &b, 4);
+            return f;
+        };
+        mn[a] = dec(hb[a]);
+        const double span = (double)dec(hb[3 + a]) - (double)mn[a];
+        if (!(span < 2097152.0)) {
+            ctx->err = std::string(what) + ": an axis spans more than 2^21 voxels";
+            return APD_EINVAL;
+        }
+    }
+    hipLaunchKernelGGL(k_voxel_keys, dim3(grid_for(n)), dim3(BLOCK), 0, s, (const float *)ctx->q_xyz.p, n, voxel,
+                       mn[0], mn[1], mn[2], (uint64_t *)ctx->q_keys.p, (int *)ctx->q_idx.p);
+    EV_OK(ctx, hipGetLastError());
+    if ((st = sort_pairs(ctx, ctx->q_keys, ctx->q_keys_s, ctx->q_idx, ctx->q_idx_s, n))) return st;
+    return APD_OK;
+}
+
 extern "C" {
 
 apd_eval_ctx *apd_eval_create(int32_t device) {
@@ -576,7 +700,8 @@ void apd_eval_destroy(apd_eval_ctx *ctx) {
     (void)hipSetDevice(ctx->device);
     for (Buf *b : {&ctx->t_xyz, &ctx->t_keys, &ctx->t_keys_s, &ctx->t_idx, &ctx->t_idx_s, &ctx->t_pts, &ctx->t_boxes,
                    &ctx->q_xyz, &ctx->q_keys, &ctx->q_keys_s, &ctx->q_idx, &ctx->q_idx_s, &ctx->q_dist, &ctx->q_aux,
-                   &ctx->sort_tmp, &ctx->small, &ctx->r_keys, &ctx->r_depth, &ctx->r_index, &ctx->r_small})
+                   &ctx->sort_tmp, &ctx->small, &ctx->r_keys, &ctx->r_depth, &ctx->r_index, &ctx->r_small, &ctx->s_dist,
+                   &ctx->s_gap, &ctx->s_cnt, &ctx->s_out})
         if (b->p) (void)hipFree(b->p);
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
     if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
@@ -762,37 +887,12 @@ int32_t apd_eval_voxel_downsample(apd_eval_ctx *ctx, int64_t n64, const float *x
     hipStream_t s = ctx->stream;
     EV_OK(ctx, hipMemcpyAsync(ctx->q_xyz.p, xyz, (size_t)n * 12, hipMemcpyDefault, s));
     EV_OK(ctx, hipEventRecord(ctx->ev0, s));
-    EV_OK(ctx, hipMemsetAsync(bounds, 0xFF, 12, s));
-    EV_OK(ctx, hipMemsetAsync(bounds + 3, 0, 12, s));
-    hipLaunchKernelGGL(k_voxel_bounds, dim3(grid_capped(n)), dim3(BLOCK), 0, s, (const float *)ctx->q_xyz.p, n, voxel,
-                       bounds);
-    EV_OK(ctx, hipGetLastError());
-    uint32_t hb[6];
-    EV_OK(ctx, hipMemcpyAsync(hb, bounds, 24, hipMemcpyDeviceToHost, s));
-    EV_OK(ctx, hipStreamSynchronize(s));
-    if (hb[0] == 0xFFFFFFFFu) {  // no finite point
+    bool none = false;
+    if ((st = voxel_sorted_keys(ctx, "apd_eval_voxel_downsample", n, voxel, bounds, none))) return st;
+    if (none) {  // no finite point
         EV_OK(ctx, hipMemcpy(n_keep, &kept, 8, hipMemcpyDefault));
         return APD_OK;
     }
-    float mn[3];
-    for (int a = 0; a < 3; ++a) {
-        auto dec = [](uint32_t u) {
-            const uint32_t b = (u & 0x80000000u) ? (u & 0x7FFFFFFFu) : ~u;
-            float f;
-            memcpy(&f, &b, 4);
-            return f;
-        };
-        mn[a] = dec(hb[a]);
-        const double span = (double)dec(hb[3 + a]) - (double)mn[a];
-        if (!(span < 2097152.0)) {
-            ctx->err = "apd_eval_voxel_downsample: an axis spans more than 2^21 voxels";
-            return APD_EINVAL;
-        }
-    }
-    hipLaunchKernelGGL(k_voxel_keys, dim3(grid_for(n)), dim3(BLOCK), 0, s, (const float *)ctx->q_xyz.p, n, voxel,
-                       mn[0], mn[1], mn[2], (uint64_t *)ctx->q_keys.p, (int *)ctx->q_idx.p);
-    EV_OK(ctx, hipGetLastError());
-    if ((st = sort_pairs(ctx, ctx->q_keys, ctx->q_keys_s, ctx->q_idx, ctx->q_idx_s, n))) return st;
     int *flag = (int *)ctx->q_dist.p, *pos = (int *)ctx->q_aux.p + 32, *keep = (int *)ctx->q_keys.p;
     EV_OK(ctx, hipMemsetAsync(flag, 0, (size_t)n * 4, s));
     hipLaunchKernelGGL(k_voxel_heads, dim3(grid_for(n)), dim3(BLOCK), 0, s, (const uint64_t *)ctx->q_keys_s.p,
@@ -991,6 +1091,175 @@ int32_t apd_eval_get_render_timing(apd_eval_ctx *ctx, double *render_ms, double 
     if (!ctx) return APD_EINVAL;
     if (render_ms) *render_ms = ctx->render_ms;
     if (visibility_ms) *visibility_ms = ctx->visibility_ms;
+    return APD_OK;
+}
+
+int32_t apd_eval_cube_cameras(const float origin[3], int32_t size, apd_camera cams[6]) {
+    if (!origin || !cams || size < 2 || size > 16384) return APD_EINVAL;
+    if (!std::isfinite(origin[0]) || !std::isfinite(origin[1]) || !std::isfinite(origin[2])) return APD_EINVAL;
+    // rows (right, down, forward) of the faces +X, -X, +Y, -Y, +Z, -Z; every determinant is +1
+    static const float kR[6][9] = {{0, 0, -1, 0, 1, 0, 1, 0, 0},  {0, 0, 1, 0, 1, 0, -1, 0, 0},
+                                   {1, 0, 0, 0, 0, -1, 0, 1, 0},  {1, 0, 0, 0, 0, 1, 0, -1, 0},
+                                   {1, 0, 0, 0, 1, 0, 0, 0, 1},   {-1, 0, 0, 0, 1, 0, 0, 0, -1}};
+    const float f = 0.5f * (float)size;  // exact
+    for (int k = 0; k < 6; ++k) {
+        apd_camera c{};
+        memcpy(c.R, kR[k], sizeof c.R);
+        for (int r = 0; r < 3; ++r)  // exact: one entry of a row is +-1, the others are 0
+            c.t[r] = -(c.R[3 * r] * origin[0] + c.R[3 * r + 1] * origin[1] + c.R[3 * r + 2] * origin[2]);
+        c.K[0] = c.K[4] = f;
+        c.K[2] = c.K[5] = f - 0.5f;
+        c.K[8] = 1.0f;
+        c.width = c.height = size;
+        cams[k] = c;
+    }
+    return APD_OK;
+}
+
+int32_t apd_eval_free_gap(apd_eval_ctx *ctx, int64_t n64, const float *xyz, int32_t num_views, const apd_camera *cams,
+                          const float *const *depth, float *gap) {
+    if (!ctx) return APD_EINVAL;
+    int st = check_n(ctx, "apd_eval_free_gap", n64, xyz);
+    if (st || (st = check_views(ctx, "apd_eval_free_gap", num_views, cams))) return st;
+    if ((n64 > 0 && !gap) || (num_views > 0 && !depth)) {
+        ctx->err = "apd_eval_free_gap: NULL gap array or depth map list";
+        return APD_EINVAL;
+    }
+    for (int v = 0; v < num_views; ++v)
+        if (!depth[v]) {
+            ctx->err = "apd_eval_free_gap: NULL depth map";
+            return APD_EINVAL;
+        }
+    ctx->free_gap_ms = 0.0;
+    const int n = (int)n64;
+    if (n == 0) return APD_OK;
+    EV_OK(ctx, hipSetDevice(ctx->device));
+    if ((st = grow(ctx, ctx->q_xyz, (size_t)n * 12)) || (st = grow(ctx, ctx->q_dist, (size_t)n * 4))) return st;
+    hipStream_t s = ctx->stream;
+    float *d_gap = (float *)ctx->q_dist.p;
+    EV_OK(ctx, hipMemcpyAsync(ctx->q_xyz.p, xyz, (size_t)n * 12, hipMemcpyDefault, s));
+    double ms = 0.0, total = 0.0;
+    int v0 = 0;
+    do {  // at least once: without views the kernel still writes -inf
+        VisViews vv{};
+        vv.n = std::min(VIS_CHUNK, num_views - v0);
+        size_t bytes = 0;
+        for (int k = 0; k < vv.n; ++k) bytes += (size_t)cams[v0 + k].width * (size_t)cams[v0 + k].height * 4;
+        if ((st = grow(ctx, ctx->r_depth, bytes))) return st;
+        size_t off = 0;
+        for (int k = 0; k < vv.n; ++k) {
+            const size_t b = (size_t)cams[v0 + k].width * (size_t)cams[v0 + k].height * 4;
+            vv.cam[k] = cams[v0 + k];
+            vv.depth[k] = (const float *)((char *)ctx->r_depth.p + off);
+            EV_OK(ctx, hipMemcpyAsync((char *)ctx->r_depth.p + off, depth[v0 + k], b, hipMemcpyDefault, s));
+            off += b;
+        }
+        EV_OK(ctx, hipEventRecord(ctx->ev0, s));
+        hipLaunchKernelGGL(k_free_gap, dim3(grid_for(n)), dim3(BLOCK), 0, s, (const float *)ctx->q_xyz.p, n, vv,
+                           v0 == 0 ? 1 : 0, d_gap);
+        EV_OK(ctx, hipGetLastError());
+        EV_OK(ctx, hipEventRecord(ctx->ev1, s));
+        EV_OK(ctx, hipStreamSynchronize(s));  // the next chunk reuses the staging buffer and the events
+        if ((st = elapsed(ctx, ms))) return st;
+        total += ms;
+        v0 += VIS_CHUNK;
+    } while (v0 < num_views);
+    EV_OK(ctx, hipMemcpyAsync(gap, d_gap, (size_t)n * 4, hipMemcpyDefault, s));
+    EV_OK(ctx, hipStreamSynchronize(s));
+    ctx->free_gap_ms = total;
+    return APD_OK;
+}
+
+int32_t apd_eval_voxel_scores(apd_eval_ctx *ctx, int64_t n64, const float *xyz, float voxel, const float *dist,
+                              const float *gap, int32_t num_tol, const float *tol, int64_t *good, int64_t *bad,
+                              uint64_t *ratio_sum, int64_t *voxels) {
+    if (!ctx) return APD_EINVAL;
+    int st = check_n(ctx, "apd_eval_voxel_scores", n64, xyz);
+    if (st) return st;
+    if (!(voxel > 0.0f) || !std::isfinite(voxel)) {
+        ctx->err = "apd_eval_voxel_scores: voxel must be positive and finite";
+        return APD_EINVAL;
+    }
+    if (n64 > 0 && !dist) {
+        ctx->err = "apd_eval_voxel_scores: NULL dist array";
+        return APD_EINVAL;
+    }
+    if (num_tol < 0 || (num_tol > 0 && !tol)) {
+        ctx->err = "apd_eval_voxel_scores: bad tolerance list";
+        return APD_EINVAL;
+    }
+    if (num_tol > 0 && (!good || !bad || !ratio_sum || !voxels)) {
+        ctx->err = "apd_eval_voxel_scores: NULL output";
+        return APD_EINVAL;
+    }
+    EV_OK(ctx, hipSetDevice(ctx->device));
+    std::vector<float> tols((size_t)num_tol);
+    if (num_tol > 0) EV_OK(ctx, hipMemcpy(tols.data(), tol, (size_t)num_tol * 4, hipMemcpyDefault));
+    for (float t : tols)
+        if (!(t >= 0.0f)) {
+            ctx->err = "apd_eval_voxel_scores: a tolerance is negative or NaN";
+            return APD_EINVAL;
+        }
+    const int n = (int)n64;
+    ctx->scores_ms = 0.0;
+    // host copy of the sums, tolerance-major: good, bad, ratio_sum, voxels
+    std::vector<unsigned long long> sums((size_t)num_tol * 4, 0ull);
+    auto deliver = [&]() -> int {
+        std::vector<unsigned long long> col((size_t)num_tol);
+        void *const outs[4] = {good, bad, ratio_sum, voxels};
+        for (int q = 0; q < 4 && num_tol > 0; ++q) {
+            for (int k = 0; k < num_tol; ++k) col[(size_t)k] = sums[(size_t)k * 4 + q];
+            EV_OK(ctx, hipMemcpy(outs[q], col.data(), (size_t)num_tol * 8, hipMemcpyDefault));
+        }
+        return APD_OK;
+    };
+    if (n == 0) return deliver();
+    if ((st = grow(ctx, ctx->q_xyz, (size_t)n * 12)) || (st = grow(ctx, ctx->q_keys, (size_t)n * 8)) ||
+        (st = grow(ctx, ctx->q_keys_s, (size_t)n * 8)) || (st = grow(ctx, ctx->q_idx, (size_t)n * 4)) ||
+        (st = grow(ctx, ctx->q_idx_s, (size_t)n * 4)) || (st = grow(ctx, ctx->q_aux, 128)) ||
+        (st = grow(ctx, ctx->s_dist, (size_t)n * 4)) || (gap && (st = grow(ctx, ctx->s_gap, (size_t)n * 4))) ||
+        (st = grow(ctx, ctx->s_cnt, (size_t)n * 8)) || (st = grow(ctx, ctx->s_out, (size_t)std::max(num_tol, 1) * 32)))
+        return st;
+    hipStream_t s = ctx->stream;
+    EV_OK(ctx, hipMemcpyAsync(ctx->q_xyz.p, xyz, (size_t)n * 12, hipMemcpyDefault, s));
+    EV_OK(ctx, hipMemcpyAsync(ctx->s_dist.p, dist, (size_t)n * 4, hipMemcpyDefault, s));
+    if (gap) EV_OK(ctx, hipMemcpyAsync(ctx->s_gap.p, gap, (size_t)n * 4, hipMemcpyDefault, s));
+    EV_OK(ctx, hipEventRecord(ctx->ev0, s));
+    bool none = false;
+    // its own scratch for the bounds, as voxel_downsample: `small` keeps the target's box
+    if ((st = voxel_sorted_keys(ctx, "apd_eval_voxel_scores", n, voxel, (uint32_t *)ctx->q_aux.p, none))) return st;
+    if (none || num_tol == 0) return deliver();
+    const uint64_t *keys = (const uint64_t *)ctx->q_keys_s.p;
+    uint64_t *cnt = (uint64_t *)ctx->s_cnt.p;
+    unsigned long long *out = (unsigned long long *)ctx->s_out.p;
+    EV_OK(ctx, hipMemsetAsync(out, 0, (size_t)num_tol * 32, s));
+    // one tolerance at a time: the scratch is one uint64 per point whatever num_tol is
+    for (int k = 0; k < num_tol; ++k) {
+        const ClassOf cls{(const int *)ctx->q_idx_s.p, (const float *)ctx->s_dist.p,
+                          gap ? (const float *)ctx->s_gap.p : nullptr, tols[(size_t)k]};
+        auto vals = rocprim::make_transform_iterator(rocprim::counting_iterator<int>(0), cls);
+        size_t tb = 0;
+        EV_OK(ctx, rocprim::inclusive_scan_by_key(nullptr, tb, keys, vals, cnt, (size_t)n, rocprim::plus<uint64_t>(),
+                                                  rocprim::equal_to<uint64_t>(), s));
+        if ((st = grow(ctx, ctx->sort_tmp, tb))) return st;
+        EV_OK(ctx, rocprim::inclusive_scan_by_key(ctx->sort_tmp.p, tb, keys, vals, cnt, (size_t)n,
+                                                  rocprim::plus<uint64_t>(), rocprim::equal_to<uint64_t>(), s));
+        hipLaunchKernelGGL(k_voxel_ratio, dim3(std::min(grid_for(n), RATIO_GRID)), dim3(BLOCK), 0, s, keys,
+                           (const uint64_t *)cnt, n,
+                           out + 4 * (size_t)k);
+        EV_OK(ctx, hipGetLastError());
+    }
+    EV_OK(ctx, hipEventRecord(ctx->ev1, s));
+    EV_OK(ctx, hipMemcpyAsync(sums.data(), out, (size_t)num_tol * 32, hipMemcpyDeviceToHost, s));
+    EV_OK(ctx, hipStreamSynchronize(s));
+    if ((st = deliver())) return st;
+    return elapsed(ctx, ctx->scores_ms);
+}
+
+int32_t apd_eval_get_protocol_timing(apd_eval_ctx *ctx, double *free_gap_ms, double *scores_ms) {
+    if (!ctx) return APD_EINVAL;
+    if (free_gap_ms) *free_gap_ms = ctx->free_gap_ms;
+    if (scores_ms) *scores_ms = ctx->scores_ms;
     return APD_OK;
 }
 

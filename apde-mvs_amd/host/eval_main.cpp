@@ -5,6 +5,8 @@
 // free-space and visibility handling is not modelled. A ground-truth cloud can be rendered into the
 // scan's cameras with a z-buffer (render mode, and --gt_cloud in depth mode), and cloud mode can
 // restrict completeness to the ground-truth points such a z-buffer test sees (--visible_views).
+// Scanner mode (--gt_mlp) reads the MeshLab project of the laser scans and scores with a scanner
+// free-space test and voxel averages, modelled on the ETH3D protocol (not the ETH3D tool itself).
 #include <algorithm>
 #include <atomic>
 #include <cmath>
@@ -64,13 +66,37 @@ const char *kHelp =
     "  size of S/APD/<id>/depths.bin when that exists, else of the image, the intrinsics rescaled\n"
     "  from the image's size as fusion does. Nearest point per pixel, ties to the lowest index.\n"
     "\n"
+    "scanner mode (uses the GPU):\n"
+    "  apd_eval --cloud REC.ply --gt_mlp SCAN.mlp [--tolerances ...] [--voxel V] [--cube_size N] [--splat s]\n"
+    "           [--max_dist D] [--accuracy_cloud_out DIR] [--completeness_cloud_out DIR] [--gpu_index G]\n"
+    "           [--json OUT.json]\n"
+    "  SCAN.mlp is a MeshLab project: one PLY per laser-scanner position with its pose (<MLMesh\n"
+    "  filename> + <MLMatrix44>), the ground-truth layout of ETH3D. G is the union of the scans in\n"
+    "  world coordinates, R the reconstruction; no cloud is down-sampled. Per tolerance t a point of\n"
+    "  R is good when dist(R_i, G) <= t, bad when it is not good and lies more than t in front of\n"
+    "  the surface a scanner saw along its ray, and unobserved otherwise (behind the scanned\n"
+    "  surface or where no beam went): unobserved points do not count. A scanner sees through the\n"
+    "  six faces of a cube map of N^2 pixels (--cube_size, default 2048), the z-buffer of ITS OWN\n"
+    "  points with footprint 2s+1 (--splat s, default 1). A point of G is good when dist(G_j, R) <= t,\n"
+    "  else bad. Accuracy and completeness are the means over the V-sized voxels (--voxel, default\n"
+    "  0.01: a scoring voxel) of good / (good + bad), as integers (good << 32) / (good + bad).\n"
+    "  Prints the lines Tolerances: / Completenesses: / Accuracies: / F1-scores: that\n"
+    "  tools/eval_eth_train.py parses. --accuracy_cloud_out / --completeness_cloud_out DIR write\n"
+    "  DIR/tolerance_<t>.ply, the points of R / G coloured green (good), red (bad), blue (unobserved).\n"
+    "  Modelled on the ETH3D protocol, NOT the ETH3D tool: a z-buffer per cube-map pixel instead of\n"
+    "  per-beam cones, a free-space margin equal to the tolerance, integer-rounded voxel ratios.\n"
+    "  Parity with that tool is unpinned; the numbers are not for published tables.\n"
+    "  --gt_mlp excludes --gt, --dense_folder, --render_gt, --visible_views and --scan.\n"
+    "\n"
     "The modes may be combined in one invocation; --json then holds all of them.\n"
     "Exit status: 0 ok, 1 run-time failure, 2 bad arguments or unreadable input.\n";
 
 struct Options {
     std::string cloud, gt, json, dense, against, gt_depth, gt_cloud, render_gt, scan, out;
+    std::string gt_mlp, accuracy_out, completeness_out;  // scanner mode
+    int cube_size = 2048;
     int splat = 0;
-    bool splat_given = false, occlusion_given = false;
+    bool splat_given = false, occlusion_given = false, voxel_given = false, cube_given = false;
     int visible_views = 0;  // 0: no visibility filter
     float occlusion_tol = 0.01f;
     std::vector<float> tol = {0.01f, 0.02f, 0.05f, 0.1f, 0.2f, 0.5f};
@@ -436,6 +462,196 @@ int run_cloud(const Options &opt, CloudInputs &in, std::string &json) {
     return 0;
 }
 
+// ---- scanner mode -------------------------------------------------------------------------------
+
+struct Scanner {
+    std::string ply;
+    std::vector<float> xyz;  // world coordinates, finite points only after run_scanners' first step
+    float origin[3] = {0, 0, 0};
+    int64_t points_in = 0;
+};
+
+struct ScannerInputs {
+    CloudInfo rec;
+    std::vector<Scanner> scanners;
+};
+
+struct SideScores {
+    int64_t n = 0;
+    std::vector<int64_t> good, bad, voxels;
+    std::vector<uint64_t> ratio_sum;
+    std::vector<double> score;
+    std::vector<float> dist;
+    double build_ms = 0.0, query_ms = 0.0, scores_ms = 0.0;
+};
+
+// set_target(t), distances(q), voxel_scores(q, dist, gap)
+bool score_side(apd_eval_ctx *ctx, const std::vector<float> &q, const std::vector<float> &t, const float *gap,
+                const Options &opt, float max_dist, SideScores &s) {
+    s.n = (int64_t)(q.size() / 3);
+    int st = apd_eval_set_target(ctx, (int64_t)(t.size() / 3), t.data());
+    if (st != APD_OK) return fail_ctx(ctx, "apd_eval_set_target", st);
+    s.dist.resize((size_t)s.n);
+    st = apd_eval_distances(ctx, s.n, q.data(), max_dist, s.dist.data(), 0, nullptr, nullptr);
+    if (st != APD_OK) return fail_ctx(ctx, "apd_eval_distances", st);
+    apd_eval_get_timing(ctx, &s.build_ms, &s.query_ms, nullptr);
+    const size_t k = opt.tol.size();
+    s.good.assign(k, 0);
+    s.bad.assign(k, 0);
+    s.voxels.assign(k, 0);
+    s.ratio_sum.assign(k, 0);
+    st = apd_eval_voxel_scores(ctx, s.n, q.data(), opt.voxel, s.dist.data(), gap, (int32_t)k, opt.tol.data(),
+                               s.good.data(), s.bad.data(), s.ratio_sum.data(), s.voxels.data());
+    if (st != APD_OK) return fail_ctx(ctx, "apd_eval_voxel_scores", st);
+    apd_eval_get_protocol_timing(ctx, nullptr, &s.scores_ms);
+    s.score.assign(k, 0.0);
+    for (size_t i = 0; i < k; ++i)
+        if (s.voxels[i] > 0) s.score[i] = (double)s.ratio_sum[i] / ((double)s.voxels[i] * 4294967296.0);
+    return true;
+}
+
+std::string json_side(const SideScores &s) {
+    auto i64 = [](int64_t v) { return std::to_string(v); };
+    std::vector<int64_t> unobs(s.good.size());
+    std::vector<double> of_all(s.good.size()), plain(s.good.size());
+    for (size_t i = 0; i < s.good.size(); ++i) {
+        unobs[i] = s.n - s.good[i] - s.bad[i];
+        of_all[i] = s.n ? (double)s.good[i] / (double)s.n : 0.0;
+        plain[i] = s.good[i] + s.bad[i] ? (double)s.good[i] / (double)(s.good[i] + s.bad[i]) : 0.0;
+    }
+    return "{\"points\": " + std::to_string(s.n) + ", \"good\": [" + join(s.good, i64) + "], \"bad\": [" +
+           join(s.bad, i64) + "], \"unobserved\": [" + join(unobs, i64) + "], \"ratio_sum\": [" +
+           join(s.ratio_sum, [](uint64_t v) { return std::to_string(v); }) + "], \"voxels\": [" + join(s.voxels, i64) +
+           "], \"score\": [" + join(s.score, fmt_g) + "], \"plain_of_all\": [" + join(of_all, fmt_g) +
+           "], \"plain\": [" + join(plain, fmt_g) + "], \"build_ms\": " + fmt_g(s.build_ms) + ", \"query_ms\": " +
+           fmt_g(s.query_ms) + ", \"scores_ms\": " + fmt_g(s.scores_ms) + "}";
+}
+
+// DIR/tolerance_<t>.ply per tolerance: green good, red bad, blue unobserved (gap == nullptr: none)
+bool write_class_clouds(const std::string &dir, const std::vector<float> &xyz, const std::vector<float> &dist,
+                        const float *gap, const std::vector<float> &tol) {
+    if (!make_dir(dir)) {
+        std::fprintf(stderr, "apd_eval: cannot create %s\n", dir.c_str());
+        return false;
+    }
+    std::vector<uint8_t> rgb(xyz.size());
+    for (float t : tol) {
+        for (size_t i = 0; i < dist.size(); ++i) {
+            const bool good = dist[i] <= t, bad = !good && (!gap || gap[i] > t);
+            rgb[3 * i] = bad ? 255 : 0;
+            rgb[3 * i + 1] = good ? 255 : 0;
+            rgb[3 * i + 2] = !good && !bad ? 255 : 0;
+        }
+        const std::string path = dir + "/tolerance_" + fmt_f32(t) + ".ply";
+        if (!write_ply_xyz_rgb(path, xyz, rgb)) {
+            std::fprintf(stderr, "apd_eval: cannot write %s\n", path.c_str());
+            return false;
+        }
+    }
+    return true;
+}
+
+// returns the exit status; appends "scanners": {...} to json
+int run_scanners(const Options &opt, ScannerInputs &in, std::string &json) {
+    CloudInfo &rec = in.rec;
+    drop_non_finite(rec);
+    std::vector<float> G;
+    for (Scanner &s : in.scanners) {
+        CloudInfo c;
+        c.xyz.swap(s.xyz);
+        drop_non_finite(c);
+        s.points_in = c.points_in;
+        s.xyz.swap(c.xyz);
+        G.insert(G.end(), s.xyz.begin(), s.xyz.end());
+    }
+    const float max_dist = opt.max_dist >= 0.0f ? opt.max_dist : *std::max_element(opt.tol.begin(), opt.tol.end());
+    apd_eval_ctx *ctx = apd_eval_create(opt.gpu);
+    if (!ctx) {
+        std::fprintf(stderr, "apd_eval: %s (device %d)\n", apd_eval_last_error(nullptr), opt.gpu);
+        return 1;
+    }
+    // the free gap of R: one scanner's six cube faces at a time, rendered from that scanner's own
+    // points, the maximum over the scanners taken here (a maximum has no order)
+    const int64_t nr = rec.points;
+    std::vector<float> gap((size_t)nr, -INFINITY), part((size_t)nr);
+    double render_ms = 0.0, gap_ms = 0.0;
+    bool ok = true;
+    for (size_t si = 0; ok && si < in.scanners.size(); ++si) {
+        const Scanner &s = in.scanners[si];
+        std::vector<ScanView> faces(6);
+        apd_camera cams[6];
+        if (apd_eval_cube_cameras(s.origin, opt.cube_size, cams) != APD_OK) {
+            std::fprintf(stderr, "apd_eval: scanner %zu has no usable origin\n", si);
+            ok = false;
+            break;
+        }
+        for (int f = 0; f < 6; ++f) faces[(size_t)f].cam = cams[f];
+        std::vector<Mat> maps;
+        if (!(ok = render_batch(ctx, s.xyz, faces, 0, 6, opt.splat, maps, render_ms))) break;
+        const float *ptrs[6];
+        for (int f = 0; f < 6; ++f) ptrs[f] = maps[(size_t)f].ptr<float>();
+        const int st = apd_eval_free_gap(ctx, nr, rec.xyz.data(), 6, cams, ptrs, part.data());
+        if (st != APD_OK) {
+            ok = fail_ctx(ctx, "apd_eval_free_gap", st);
+            break;
+        }
+        double ms = 0.0;
+        apd_eval_get_protocol_timing(ctx, &ms, nullptr);
+        gap_ms += ms;
+        for (size_t i = 0; i < gap.size(); ++i) gap[i] = std::max(gap[i], part[i]);
+    }
+    SideScores acc, comp;
+    ok = ok && score_side(ctx, rec.xyz, G, gap.data(), opt, max_dist, acc) &&
+         score_side(ctx, G, rec.xyz, nullptr, opt, max_dist, comp);
+    apd_eval_destroy(ctx);
+    if (!ok) return 1;
+    if (!opt.accuracy_out.empty() && !write_class_clouds(opt.accuracy_out, rec.xyz, acc.dist, gap.data(), opt.tol))
+        return 1;
+    if (!opt.completeness_out.empty() && !write_class_clouds(opt.completeness_out, G, comp.dist, nullptr, opt.tol))
+        return 1;
+
+    const size_t k = opt.tol.size();
+    std::vector<double> f(k);
+    for (size_t i = 0; i < k; ++i) {
+        const double a = acc.score[i], c = comp.score[i];
+        f[i] = a + c > 0.0 ? 2.0 * a * c / (a + c) : 0.0;
+    }
+    auto six = [](double v) {
+        char b[64];
+        std::snprintf(b, sizeof b, "%.6f", v);
+        return std::string(b);
+    };
+    std::printf("Scanner free-space model: %zu scanner positions, cube maps of %d^2, voxel %s\n", in.scanners.size(),
+                opt.cube_size, fmt_f32(opt.voxel).c_str());
+    std::printf("%-10s %10s %10s %10s %9s   %10s %10s %9s\n", "tolerance", "acc good", "acc bad", "unobserved", "accuracy",
+                "comp good", "comp bad", "complete");
+    for (size_t i = 0; i < k; ++i)
+        std::printf("%-10s %10lld %10lld %10lld %9.6f   %10lld %10lld %9.6f\n", fmt_f32(opt.tol[i]).c_str(),
+                    (long long)acc.good[i], (long long)acc.bad[i], (long long)(acc.n - acc.good[i] - acc.bad[i]),
+                    acc.score[i], (long long)comp.good[i], (long long)comp.bad[i], comp.score[i]);
+    std::printf("Tolerances: %s\n", join(opt.tol, fmt_f32, " ").c_str());
+    std::printf("Completenesses: %s\n", join(comp.score, six, " ").c_str());
+    std::printf("Accuracies: %s\n", join(acc.score, six, " ").c_str());
+    std::printf("F1-scores: %s\n", join(f, six, " ").c_str());
+    json += "\"scanners\": {\"definition\": \"scanner free-space model and voxel-averaged scores, modelled on the ETH3D "
+            "protocol (a z-buffer per cube-map pixel, a free-space margin equal to the tolerance, integer voxel "
+            "ratios); parity with the ETH3D tool is not pinned\", \"tolerances\": [" +
+            join(opt.tol, fmt_f32) + "], \"max_dist\": " + fmt_g((double)max_dist) + ", \"voxel\": " +
+            fmt_g((double)opt.voxel) + ", \"cube_size\": " + std::to_string(opt.cube_size) + ", \"splat\": " +
+            std::to_string(opt.splat) + ", \"rec\": " + json_cloud(rec) + ", \"gt\": {\"points\": " +
+            std::to_string(G.size() / 3) + "}, \"positions\": [" +
+            join(in.scanners,
+                 [](const Scanner &s) {
+                     return "{\"ply\": \"" + esc(s.ply) + "\", \"points_in\": " + std::to_string(s.points_in) +
+                            ", \"points\": " + std::to_string(s.xyz.size() / 3) + ", \"origin\": [" +
+                            fmt_g((double)s.origin[0]) + ", " + fmt_g((double)s.origin[1]) + ", " +
+                            fmt_g((double)s.origin[2]) + "]}";
+                 }) +
+            "], \"accuracy\": " + json_side(acc) + ", \"completeness\": " + json_side(comp) + ", \"f1\": [" +
+            join(f, fmt_g) + "], \"render_ms\": " + fmt_g(render_ms) + ", \"free_gap_ms\": " + fmt_g(gap_ms) + "}";
+    return 0;
+}
+
 // ---- depth mode ---------------------------------------------------------------------------------
 
 struct DepthStats {
@@ -649,6 +865,14 @@ int main(int argc, char **argv) {
         else if (a == "--scan") opt.scan = v;
         else if (a == "--out") opt.out = v;
         else if (a == "--gpu_index") opt.gpu = std::atoi(v.c_str());
+        else if (a == "--gt_mlp") opt.gt_mlp = v;
+        else if (a == "--accuracy_cloud_out") opt.accuracy_out = v;
+        else if (a == "--completeness_cloud_out") opt.completeness_out = v;
+        else if (a == "--cube_size") {
+            if (!parse_int(v, opt.cube_size) || opt.cube_size < 2 || opt.cube_size > 16384)
+                return bad("bad --cube_size " + v + " (2..16384)");
+            opt.cube_given = true;
+        }
         else if (a == "--splat") {
             if (!parse_int(v, opt.splat) || opt.splat < 0 || opt.splat > 16) return bad("bad --splat " + v + " (0..16)");
             opt.splat_given = true;
@@ -663,6 +887,7 @@ int main(int argc, char **argv) {
         } else if (a == "--voxel") {
             if (!parse_float(v, opt.voxel) || !(opt.voxel >= 0.0f) || !std::isfinite(opt.voxel))
                 return bad("bad --voxel " + v);
+            opt.voxel_given = true;
         } else if (a == "--tolerances") {
             opt.tol.clear();
             std::istringstream ss(v);
@@ -677,10 +902,25 @@ int main(int argc, char **argv) {
             return bad("unknown option " + a);
         }
     }
-    const bool cloud_mode = !opt.cloud.empty() || !opt.gt.empty();
+    const bool scanner_mode = !opt.gt_mlp.empty();
+    const bool cloud_mode = !scanner_mode && (!opt.cloud.empty() || !opt.gt.empty());
     const bool depth_mode = !opt.dense.empty() || !opt.against.empty() || !opt.gt_depth.empty() || !opt.gt_cloud.empty();
     const bool render_mode = !opt.render_gt.empty();
-    if (!cloud_mode && !depth_mode && !render_mode) return bad("nothing to do");
+    if (scanner_mode) {
+        if (opt.cloud.empty()) return bad("scanner mode needs --cloud and --gt_mlp");
+        if (!opt.gt.empty() || depth_mode || render_mode)
+            return bad("--gt_mlp excludes --gt, --dense_folder and --render_gt");
+        if (opt.visible_views > 0 || !opt.scan.empty()) return bad("--gt_mlp does not take --visible_views / --scan");
+        if (!opt.voxel_given) opt.voxel = 0.01f;  // the scoring voxel
+        if (!(opt.voxel > 0.0f)) return bad("--gt_mlp needs a positive --voxel");
+        if (!opt.splat_given) opt.splat = 1;
+        if (opt.max_dist >= 0.0f)
+            for (float t : opt.tol)
+                if (t > opt.max_dist) return bad("a tolerance exceeds --max_dist");
+    } else if (opt.cube_given || !opt.accuracy_out.empty() || !opt.completeness_out.empty()) {
+        return bad("--cube_size / --accuracy_cloud_out / --completeness_cloud_out without --gt_mlp");
+    }
+    if (!cloud_mode && !depth_mode && !render_mode && !scanner_mode) return bad("nothing to do");
     if (cloud_mode && (opt.cloud.empty() || opt.gt.empty())) return bad("cloud mode needs --cloud and --gt");
     if (depth_mode && (opt.dense.empty() ||
                        (int)!opt.against.empty() + (int)!opt.gt_depth.empty() + (int)!opt.gt_cloud.empty() != 1))
@@ -691,7 +931,7 @@ int main(int argc, char **argv) {
         return bad("--visible_views needs cloud mode and --scan");
     if (!opt.scan.empty() && !render_mode && opt.visible_views == 0)
         return bad("--scan with nothing that uses it (--render_gt or --visible_views)");
-    if (opt.splat_given && !render_mode && opt.visible_views == 0 && opt.gt_cloud.empty())
+    if (opt.splat_given && !render_mode && opt.visible_views == 0 && opt.gt_cloud.empty() && !scanner_mode)
         return bad("--splat with nothing that renders");
     if (opt.occlusion_given && opt.visible_views == 0) return bad("--occlusion_tol without --visible_views");
     if (cloud_mode && opt.max_dist >= 0.0f)
@@ -702,6 +942,7 @@ int main(int argc, char **argv) {
     DepthInputs din;
     CloudInputs cin;
     RenderInputs rin;
+    ScannerInputs sin;
     std::string err;
     auto unreadable = [&] {
         std::fprintf(stderr, "apd_eval: %s\n", err.c_str());
@@ -719,6 +960,21 @@ int main(int argc, char **argv) {
     }
     if (render_mode && (!read_ply_xyz(opt.render_gt, rin.xyz, err) || !load_scan_views(opt.scan, rin.views, err)))
         return unreadable();
+    if (scanner_mode) {
+        std::vector<MlpMesh> meshes;
+        if (!read_ply_xyz(opt.cloud, sin.rec.xyz, err) || !read_mlp(opt.gt_mlp, meshes, err)) return unreadable();
+        for (const MlpMesh &m : meshes) {
+            Scanner s;
+            s.ply = m.ply_path;
+            if (!read_ply_xyz(m.ply_path, s.xyz, err)) return unreadable();
+            mlp_to_world(m, s.xyz, s.origin);
+            if (!std::isfinite(s.origin[0]) || !std::isfinite(s.origin[1]) || !std::isfinite(s.origin[2])) {
+                err = opt.gt_mlp + ": the scanner position of " + m.ply_path + " is not finite";
+                return unreadable();
+            }
+            sin.scanners.push_back(std::move(s));
+        }
+    }
 
     std::string json = "{";
     int status = 0;
@@ -737,6 +993,12 @@ int main(int argc, char **argv) {
         const int st = run_cloud(opt, cin, json);
         status = std::max(status, st);
         if (st != 0) json += "\"cloud\": null";
+    }
+    if (scanner_mode) {
+        sep();
+        const int st = run_scanners(opt, sin, json);
+        status = std::max(status, st);
+        if (st != 0) json += "\"scanners\": null";
     }
     if (render_mode) {
         sep();

@@ -7,7 +7,9 @@
 #include <sys/stat.h>
 
 #include <algorithm>
+#include <cctype>
 #include <climits>
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <fstream>
@@ -317,6 +319,102 @@ bool read_ply_xyz(const std::string &path, std::vector<float> &xyz, std::string 
         done += m;
     }
     return true;
+}
+
+bool write_ply_xyz_rgb(const std::string &path, const std::vector<float> &xyz, const std::vector<uint8_t> &rgb) {
+    if (xyz.size() % 3 != 0 || rgb.size() != xyz.size()) return false;
+    std::ofstream out(path, std::ios::binary);
+    if (!out) return false;
+    const size_t n = xyz.size() / 3;
+    out << "ply\nformat binary_little_endian 1.0\nelement vertex " << n
+        << "\nproperty float x\nproperty float y\nproperty float z\nproperty uchar red\nproperty uchar green\n"
+           "property uchar blue\nend_header\n";
+    const size_t chunk = 1 << 16;
+    std::vector<char> buf(chunk * 15);
+    for (size_t done = 0; done < n;) {
+        const size_t m = std::min(chunk, n - done);
+        for (size_t i = 0; i < m; ++i) {
+            memcpy(&buf[i * 15], &xyz[3 * (done + i)], 12);
+            memcpy(&buf[i * 15 + 12], &rgb[3 * (done + i)], 3);
+        }
+        out.write(buf.data(), (std::streamsize)(m * 15));
+        done += m;
+    }
+    out.flush();
+    return (bool)out;
+}
+
+bool read_mlp(const std::string &path, std::vector<MlpMesh> &meshes, std::string &err) {
+    meshes.clear();
+    std::ifstream in(path, std::ios::binary);
+    if (!in) { err = "cannot open " + path; return false; }
+    auto fail = [&](const std::string &what) { err = path + ": " + what; meshes.clear(); return false; };
+    std::string text;
+    for (char buf[1 << 16]; in.read(buf, sizeof buf) || in.gcount() > 0;) {  // a directory opens but does not read
+        text.append(buf, (size_t)in.gcount());
+        if (text.size() > ((size_t)64 << 20)) return fail("project file larger than 64 MiB");
+    }
+    if (in.bad()) return fail("read error");
+    const size_t slash = path.find_last_of('/');
+    const std::string dir = slash == std::string::npos ? std::string(".") : path.substr(0, slash);
+    // the next "<MLMesh" that is a whole tag name, from `from` on
+    auto next_mesh = [&](size_t from) {
+        for (size_t p; (p = text.find("<MLMesh", from)) != std::string::npos; from = p + 1) {
+            const size_t e = p + 7;
+            if (e >= text.size() || text[e] == '>' || text[e] == '/' || std::isspace((unsigned char)text[e])) return p;
+        }
+        return std::string::npos;
+    };
+    for (size_t p = next_mesh(0); p != std::string::npos;) {
+        const std::string which = "mesh " + std::to_string(meshes.size() + 1);
+        const size_t tag_end = text.find('>', p);
+        if (tag_end == std::string::npos) return fail(which + ": unterminated <MLMesh tag");
+        const size_t next = next_mesh(tag_end);
+        const size_t body_end = next == std::string::npos ? text.size() : next;
+        MlpMesh m;
+        {  // the attribute filename="F" of the tag
+            const std::string tag = text.substr(p, tag_end - p);
+            size_t a = std::string::npos;
+            for (size_t q = 0; (q = tag.find("filename=\"", q)) != std::string::npos; ++q)
+                if (q > 0 && std::isspace((unsigned char)tag[q - 1])) { a = q + 10; break; }
+            const size_t b = a == std::string::npos ? a : tag.find('"', a);
+            if (b == std::string::npos || b == a) return fail(which + ": no filename attribute");
+            const std::string f = tag.substr(a, b - a);
+            m.ply_path = f[0] == '/' ? f : dir + "/" + f;
+        }
+        const size_t ms = text.find("<MLMatrix44>", tag_end);
+        if (ms == std::string::npos || ms >= body_end) return fail(which + " (" + m.ply_path + ") has no <MLMatrix44>");
+        const size_t me = text.find("</MLMatrix44>", ms);
+        if (me == std::string::npos || me > body_end) return fail(which + ": unterminated <MLMatrix44>");
+        std::istringstream nums(text.substr(ms + 12, me - ms - 12));
+        std::string tok;
+        int k = 0;
+        while (nums >> tok) {
+            char *end = nullptr;
+            const double v = std::strtod(tok.c_str(), &end);
+            if (!end || *end != '\0' || end == tok.c_str() || !std::isfinite(v))
+                return fail(which + ": '" + tok.substr(0, 32) + "' in the matrix is not a number");
+            if (k >= 16) return fail(which + ": more than 16 numbers in the matrix");
+            m.M[k++] = v;
+        }
+        if (k < 16) return fail(which + ": " + std::to_string(k) + " numbers in the matrix, 16 expected");
+        if (m.M[12] != 0.0 || m.M[13] != 0.0 || m.M[14] != 0.0 || m.M[15] != 1.0)
+            return fail(which + ": the last row of the matrix is not 0 0 0 1");
+        meshes.push_back(m);
+        p = next;
+    }
+    if (meshes.empty()) return fail("no <MLMesh> in the project");
+    return true;
+}
+
+void mlp_to_world(const MlpMesh &m, std::vector<float> &xyz, float origin[3]) {
+    const double *M = m.M;
+    for (size_t i = 0; i + 2 < xyz.size(); i += 3) {
+        const double x = xyz[i], y = xyz[i + 1], z = xyz[i + 2];
+        for (int r = 0; r < 3; ++r)  // in double, rounded once
+            xyz[i + r] = (float)(M[4 * r] * x + M[4 * r + 1] * y + M[4 * r + 2] * z + M[4 * r + 3]);
+    }
+    for (int r = 0; r < 3; ++r) origin[r] = (float)M[4 * r + 3];
 }
 
 std::string format_index(int id) {

@@ -105,6 +105,24 @@ bool read_pair_file(const std::string &dense_folder, std::vector<Problem> &probl
 // the file does not hold.
 bool read_ply_xyz(const std::string &path, std::vector<float> &xyz, std::string &err);
 
+// binary_little_endian PLY of 15-byte records float x, y, z + uchar red, green, blue (rgb: three
+// bytes per point); read_ply_xyz reads it back
+bool write_ply_xyz_rgb(const std::string &path, const std::vector<float> &xyz, const std::vector<uint8_t> &rgb);
+
+// One scanner position of a MeshLab project (.mlp): the PLY of its points and its pose.
+struct MlpMesh {
+    std::string ply_path;  // as given if absolute, else relative to the project file's directory
+    double M[16];          // <MLMatrix44>, row-major: mesh coordinates -> world
+};
+// Every <MLMesh ... filename="F" ...> with its <MLMatrix44> of 16 numbers separated by white space
+// (line breaks included). No XML library: the tags are scanned for. Rejected with a message in
+// `err`: an unreadable file, no mesh, a mesh without filename or matrix, fewer or more than 16
+// numbers, a token that is not a finite number, a last row other than 0 0 0 1.
+bool read_mlp(const std::string &path, std::vector<MlpMesh> &meshes, std::string &err);
+// xyz (mesh coordinates, from read_ply_xyz) -> world: M (x, y, z, 1) evaluated in double left to
+// right and rounded once to float. origin = the translation column rounded to float: the scanner.
+void mlp_to_world(const MlpMesh &m, std::vector<float> &xyz, float origin[3]);
+
 std::string format_index(int id);  // ToFormatIndex: %08d
 bool file_exists(const std::string &p);
 bool make_dir(const std::string &p);

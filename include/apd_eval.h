@@ -7,6 +7,8 @@
  * down-sampling of a cloud. It is the plain nearest-neighbour definition (DTU-style); the ETH3D
  * tool's free-space and visibility handling is not modelled. A z-buffer renderer of a cloud into
  * cameras and a per-point visibility count against depth maps serve a plain visibility filter.
+ * A scanner free-space test and voxel-averaged scores, modelled on the ETH3D protocol with a contract
+ * of their own, are declared at the end of this header (parity with the ETH3D tool is not pinned).
  *
  * Distance contract (bit for bit, all arithmetic fp32 and nothing contracted):
  *   - a target with a non-finite coordinate never matches; a query with one gives +inf
@@ -109,6 +111,69 @@ int32_t apd_eval_visibility(apd_eval_ctx *ctx, int64_t n, const float *xyz, int3
 /* Device-event times of the last render_depth (sort + per view: clear, splat, resolve) and
    visibility (kernels only) call, in ms. Any pointer may be NULL. */
 int32_t apd_eval_get_render_timing(apd_eval_ctx *ctx, double *render_ms, double *visibility_ms);
+
+/* ---- scanner free-space model and voxel-averaged scores -------------------------------------------
+ * Modelled on the ETH3D multi-view evaluation protocol, with this project's own exact contract (bit
+ * for bit; fp32, nothing contracted, sums left to right; integer sums only, so every output is the
+ * same from run to run). It differs from the ETH3D tool in known ways (a z-buffer per cube-map pixel
+ * instead of per-beam cones, a free-space margin equal to the tolerance, integer-rounded voxel
+ * ratios), and parity with that tool is not pinned: neither the tool nor a scan with its output is
+ * at hand.
+ *
+ * A scanner position is the six 90-degree pinhole faces of a cube map (apd_eval_cube_cameras); the
+ * scanner's own points are rendered into them with apd_eval_render_depth. A beam from the scanner to
+ * one of its points proves free space along that ray, so a reconstructed point that lies in front of
+ * the rendered depth by more than the tolerance is in observed free space.
+ *
+ * Free gap of point i against a set of views with depth maps:
+ *   gap_i = max over the views v in which the point is not dropped, its centre pixel (u, v) lies
+ *           inside the image and zb = depth_v[v*W + u] > 0 (a NaN zb compares false) of zb - d
+ *           (one fp32 subtraction); -inf if there is no such view.
+ *   Projection, drop rule and rounding are those of the visibility contract above. A +inf map entry
+ *   gives +inf, equal operands give +0; no operand is NaN, so the maximum has no order.
+ *
+ * Voxel scores. The voxel of a point is apd_eval_voxel_downsample's; a point with a non-finite
+ * coordinate belongs to no voxel and is counted nowhere. Per tolerance k and point i:
+ *   good iff dist_i <= tol_k;  bad iff not good and (gap == NULL or gap_i > tol_k);  otherwise the
+ *   point is unobserved. A NaN in dist or gap compares false.
+ * Per voxel: a = its good points, b = its bad points; it counts for k iff a + b > 0, with the
+ * integer ratio (a << 32) / (a + b) (uint64 division, rounded down).
+ *   good[k], bad[k] = totals over all voxels; ratio_sum[k] = the exact integer sum of the counted
+ *   voxels' ratios (< 2^63 for n <= 2^31); voxels[k] = their number.
+ *   score_k = ratio_sum[k] / (voxels[k] * 2^32) in double on the host, 0 when voxels[k] is 0.
+ */
+
+/* The six faces of a cube map of size x size pixels centred at origin, in the order +X, -X, +Y, -Y,
+   +Z, -Z. Rows of R (right, down, forward):
+     +X (0,0,-1) (0,1,0) (1,0,0)     -X (0,0,1) (0,1,0) (-1,0,0)
+     +Y (1,0,0) (0,0,-1) (0,1,0)     -Y (1,0,0) (0,0,1) (0,-1,0)
+     +Z (1,0,0) (0,1,0) (0,0,1)      -Z (-1,0,0) (0,1,0) (0,0,-1)
+   t = -(R origin), exact; K = [[size/2, 0, size/2 - 0.5], [0, size/2, size/2 - 0.5], [0, 0, 1]];
+   width = height = size; every other field is 0. With the projection and rounding above a face
+   spans exactly +-45 degrees: every direction lands in at least one face, a few on the seams in two.
+   Host only: needs no context and no device.
+   APD_EINVAL: size outside 2..16384, a non-finite origin, a NULL pointer. */
+int32_t apd_eval_cube_cameras(const float origin[3], int32_t size, apd_camera cams[6]);
+
+/* gap (n floats): the free gap of every point against depth[v] in cams[v]. xyz, depth[v] and gap may
+   be host or device pointers; needs no apd_eval_set_target.
+   APD_EINVAL: as apd_eval_visibility, with gap in place of seen. */
+int32_t apd_eval_free_gap(apd_eval_ctx *ctx, int64_t n, const float *xyz, int32_t num_views,
+                          const apd_camera *cams, const float *const *depth, float *gap);
+
+/* Voxel scores of n points with their distances (and free gaps; gap may be NULL: every point that
+   is not good is bad). good, bad, ratio_sum, voxels: num_tol entries each. Every data pointer may be
+   a host or a device pointer; needs no apd_eval_set_target. Tolerances need not be sorted.
+   APD_EINVAL: n out of range, xyz or dist NULL with n > 0, voxel <= 0 or not finite, an axis whose
+   occupied voxel indices span more than 2^21, num_tol < 0, tol or an output NULL with num_tol > 0,
+   a tol[k] negative or NaN. */
+int32_t apd_eval_voxel_scores(apd_eval_ctx *ctx, int64_t n, const float *xyz, float voxel, const float *dist,
+                              const float *gap, int32_t num_tol, const float *tol, int64_t *good, int64_t *bad,
+                              uint64_t *ratio_sum, int64_t *voxels);
+
+/* Device-event times of the last free_gap (kernels only) and voxel_scores (keys, sort, scans and
+   sums) call, in ms. Any pointer may be NULL. */
+int32_t apd_eval_get_protocol_timing(apd_eval_ctx *ctx, double *free_gap_ms, double *scores_ms);
 
 #ifdef __cplusplus
 }
