@@ -236,6 +236,12 @@ EVAL_EXPORTS = ["apd_eval_create", "apd_eval_destroy", "apd_eval_last_error", "a
                 "apd_eval_cube_cameras", "apd_eval_free_gap", "apd_eval_voxel_scores",
                 "apd_eval_get_protocol_timing"]
 
+# include/apd_prep.h
+PREP_EXPORTS = ["apd_prep_create", "apd_prep_destroy", "apd_prep_last_error", "apd_prep_set_model",
+                "apd_prep_pair_counts", "apd_prep_depth_ranks", "apd_prep_get_timing", "apd_prep_cos_gate"]
+PREP_MAX_IMAGES = 16384
+PREP_ATOMICS_DEFAULT, PREP_ATOMICS_GLOBAL, PREP_ATOMICS_LDS = 0, 1, 2
+
 
 def camera_from_values(v) -> ApdCamera:
     """ApdCamera from a dict of its field values (synth.camera_struct_values)."""
@@ -372,6 +378,25 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
                                           C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.apd_eval_get_protocol_timing.restype = C.c_int32
     lib.apd_eval_get_protocol_timing.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    # include/apd_prep.h
+    lib.apd_prep_create.restype = C.c_void_p
+    lib.apd_prep_create.argtypes = [C.c_int32]
+    lib.apd_prep_destroy.argtypes = [C.c_void_p]
+    lib.apd_prep_last_error.restype = C.c_char_p
+    lib.apd_prep_last_error.argtypes = [C.c_void_p]
+    lib.apd_prep_set_model.restype = C.c_int32
+    lib.apd_prep_set_model.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                       C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+    lib.apd_prep_pair_counts.restype = C.c_int32
+    lib.apd_prep_pair_counts.argtypes = [C.c_void_p, C.c_double, C.c_int32, C.c_void_p, C.c_void_p,
+                                         C.POINTER(C.c_uint64)]
+    lib.apd_prep_depth_ranks.restype = C.c_int32
+    lib.apd_prep_depth_ranks.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.apd_prep_get_timing.restype = C.c_int32
+    lib.apd_prep_get_timing.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                        C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    lib.apd_prep_cos_gate.restype = C.c_double
+    lib.apd_prep_cos_gate.argtypes = [C.c_double]
     return lib
 
 
@@ -696,6 +721,189 @@ class EvalEngine:
             self.close()
         except Exception:
             pass
+
+
+def prep_cos_gate(degrees: float = 1.0, lib: Optional[C.CDLL] = None) -> float:
+    """apd_prep_cos_gate: the smallest double q with (180/pi)*acos(q) < degrees. Host only."""
+    return float((lib or load_library()).apd_prep_cos_gate(float(degrees)))
+
+
+class PrepEngine:
+    """One apd_prep_ctx (include/apd_prep.h): pair counts by tracks and per-image depth order
+    statistics of a sparse model. All arrays are numpy, in the layout of apd_prep_set_model."""
+
+    def __init__(self, device: int = 0, lib: Optional[C.CDLL] = None):
+        self.lib = lib or load_library()
+        self.device = device
+        self.n_images = 0
+        self.ctx = self.lib.apd_prep_create(device)
+        if not self.ctx:
+            raise ApdError("apd_prep_create failed: " + (self.lib.apd_prep_last_error(None) or b"?").decode())
+
+    def _check(self, st: int, what: str):
+        if st != 0:
+            msg = (self.lib.apd_prep_last_error(self.ctx) or b"").decode()
+            raise ApdError(f"{what} -> {STATUS.get(st, st)}: {msg}")
+
+    def set_model(self, rot, trans, centres, xyz, obs_offset, obs_point):
+        r = np.ascontiguousarray(rot, np.float64).reshape(-1)
+        t = np.ascontiguousarray(trans, np.float64).reshape(-1)
+        c = np.ascontiguousarray(centres, np.float64).reshape(-1)
+        x = np.ascontiguousarray(xyz, np.float64).reshape(-1)
+        off = np.ascontiguousarray(obs_offset, np.int64).reshape(-1)
+        pt = np.ascontiguousarray(obs_point, np.int32).reshape(-1)
+        n = len(off) - 1
+        if len(r) != 9 * n or len(t) != 3 * n or len(c) != 3 * n or len(x) % 3:
+            raise ValueError("rot is (n, 3, 3), trans and centres (n, 3), xyz (m, 3), obs_offset n + 1 entries")
+        self._check(self.lib.apd_prep_set_model(self.ctx, n, r.ctypes.data, t.ctypes.data, c.ctypes.data, len(x) // 3,
+                                                x.ctypes.data if len(x) else None, len(pt), off.ctypes.data,
+                                                pt.ctypes.data if len(pt) else None), "apd_prep_set_model")
+        self.n_images = n
+
+    def pair_counts(self, q_gate: float, atomics: int = PREP_ATOMICS_DEFAULT):
+        """(shared, narrow) uint32 (n, n); self.n_records = the number of pair records."""
+        n = self.n_images
+        shared = np.empty((max(n, 1), max(n, 1)), np.uint32)
+        narrow = np.empty_like(shared)
+        rec = C.c_uint64(0)
+        self._check(self.lib.apd_prep_pair_counts(self.ctx, q_gate, atomics, shared.ctypes.data, narrow.ctypes.data,
+                                                  C.byref(rec)), "apd_prep_pair_counts")
+        self.n_records = rec.value
+        return shared, narrow
+
+    def depth_ranks(self, fractions):
+        """(z_at float64 (n, k), n_obs int64 (n,))"""
+        f = np.ascontiguousarray(fractions, np.float64).reshape(-1)
+        n = self.n_images
+        z = np.zeros((max(n, 1), max(len(f), 1)), np.float64)
+        cnt = np.zeros(max(n, 1), np.int64)
+        self._check(self.lib.apd_prep_depth_ranks(self.ctx, len(f), f.ctypes.data if len(f) else None, z.ctypes.data,
+                                                  cnt.ctypes.data), "apd_prep_depth_ranks")
+        return z, cnt
+
+    def timing(self) -> dict:
+        a, b, r, c = C.c_double(), C.c_double(), C.c_double(), C.c_double()
+        self._check(self.lib.apd_prep_get_timing(self.ctx, C.byref(a), C.byref(b), C.byref(r), C.byref(c)),
+                    "apd_prep_get_timing")
+        return {"tracks_ms": a.value, "pairs_ms": b.value, "records_ms": r.value, "ranks_ms": c.value}
+
+    def close(self):
+        if self.ctx:
+            self.lib.apd_prep_destroy(self.ctx)
+            self.ctx = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def prep_rotation(qvec) -> np.ndarray:
+    """(n, 4) quaternions (w, x, y, z), not normalised -> (n, 3, 3) R by include/apd_prep.h's formula."""
+    q = np.asarray(qvec, np.float64).reshape(-1, 4)
+    w, x, y, z = q[:, 0], q[:, 1], q[:, 2], q[:, 3]
+    R = np.empty((len(q), 3, 3), np.float64)
+    R[:, 0, 0] = (1 - 2 * (y * y)) - 2 * (z * z)
+    R[:, 0, 1] = (2 * x) * y - (2 * w) * z
+    R[:, 0, 2] = (2 * z) * x + (2 * w) * y
+    R[:, 1, 0] = (2 * x) * y + (2 * w) * z
+    R[:, 1, 1] = (1 - 2 * (x * x)) - 2 * (z * z)
+    R[:, 1, 2] = (2 * y) * z - (2 * w) * x
+    R[:, 2, 0] = (2 * z) * x - (2 * w) * y
+    R[:, 2, 1] = (2 * y) * z + (2 * w) * x
+    R[:, 2, 2] = (1 - 2 * (x * x)) - 2 * (y * y)
+    return R
+
+
+def prep_model_arrays(images, point_ids, xyz) -> dict:
+    """COLMAP-style model -> the arrays of apd_prep_set_model. images: dicts with id, qvec (w, x, y, z),
+    tvec and point_ids (the 2D points' int64 point ids, -1 = none), in any order; point_ids / xyz: the
+    3D points' ids and (m, 3) positions. Images are renumbered in ascending id. A point id an image
+    names that is not among point_ids is an error."""
+    order = sorted(range(len(images)), key=lambda i: int(images[i]["id"]))
+    if len({int(im["id"]) for im in images}) != len(images):
+        raise ValueError("duplicate image id")
+    pid = np.asarray(point_ids, np.int64).reshape(-1)
+    srt = np.argsort(pid, kind="stable")
+    spid = pid[srt]
+    if len(spid) > 1 and np.any(spid[1:] == spid[:-1]):
+        raise ValueError("duplicate point id")
+    q = np.array([images[i]["qvec"] for i in order], np.float64).reshape(-1, 4)
+    t = np.array([images[i]["tvec"] for i in order], np.float64).reshape(-1, 3)
+    R = prep_rotation(q)
+    c = np.stack([-((R[:, 0, k] * t[:, 0] + R[:, 1, k] * t[:, 1]) + R[:, 2, k] * t[:, 2]) for k in range(3)], 1)
+    off = [0]
+    obs = []
+    for i in order:
+        ids = np.asarray(images[i]["point_ids"], np.int64).reshape(-1)
+        ids = ids[ids != -1]
+        pos = np.searchsorted(spid, ids)
+        bad = (pos >= len(spid)) | (spid[np.minimum(pos, max(len(spid) - 1, 0))] != ids) if len(spid) else ids == ids
+        if np.any(bad):
+            raise ValueError(f"image {int(images[i]['id'])} names point {int(ids[bad][0])}, which points3D lacks")
+        obs.append(srt[pos].astype(np.int32))
+        off.append(off[-1] + len(ids))
+    return {"ids": [int(images[i]["id"]) for i in order], "rot": R, "trans": t, "centres": c,
+            "xyz": np.asarray(xyz, np.float64).reshape(-1, 3), "obs_offset": np.asarray(off, np.int64),
+            "obs_point": np.concatenate(obs) if obs else np.zeros(0, np.int32)}
+
+
+def prep_score(shared, narrow) -> np.ndarray:
+    """score = shared, 0 where narrow >= floor(3*shared/4) + 1 (include/apd_prep.h)."""
+    s = np.asarray(shared, np.int64)
+    return np.where(np.asarray(narrow, np.int64) >= (3 * s) // 4 + 1, 0, s)
+
+
+def prep_select(score, max_views: int = 20):
+    """Per view i the first min(max_views, n-1) of j != i by (score descending, j ascending): lists of (j, score)."""
+    n = len(score)
+    out = []
+    for i in range(n):
+        cand = sorted((j for j in range(n) if j != i), key=lambda j: (-int(score[i][j]), j))
+        out.append([(j, int(score[i][j])) for j in cand[:min(max_views, n - 1)]])
+    return out
+
+
+def prep_select_sequential(n: int, k: int = 5):
+    """The reference's sequential window (tools/colmap2mvsnet.py:453-468)."""
+    out = []
+    lim = min(n - 1, 2 * k)
+    for i in range(n):
+        nb = []
+        for offset in range(1, k + 1):
+            for direction in (-1, 1):
+                j = i + direction * offset
+                if 0 <= j < n:
+                    nb.append((j, k + 1 - offset))
+        nb.sort(key=lambda it: (-it[1], abs(it[0] - i)))
+        out.append(nb[:lim])
+    return out
+
+
+def prepare_views(images, point_ids, xyz, max_views: int = 20, sequential: bool = False, sequential_k: int = 5,
+                  device: int = 0, engine: Optional[PrepEngine] = None) -> dict:
+    """The sequence of host/prepare_main.cpp: model arrays, depth ranks (0.01, 0.99) -> depth_min /
+    depth_max, and the view selection (pair counts -> score -> selection, or the sequential window)."""
+    m = prep_model_arrays(images, point_ids, xyz)
+    eng = engine or PrepEngine(device)
+    try:
+        eng.set_model(m["rot"], m["trans"], m["centres"], m["xyz"], m["obs_offset"], m["obs_point"])
+        z, cnt = eng.depth_ranks([0.01, 0.99])
+        has = cnt > 0
+        out = {"model": m, "n_obs": cnt, "depth_min": np.where(has, z[:, 0] * 0.75, 0.0),
+               "depth_max": np.where(has, z[:, 1] * 1.25, 0.0)}
+        if sequential:
+            out["selection"] = prep_select_sequential(len(m["ids"]), sequential_k)
+        else:
+            shared, narrow = eng.pair_counts(prep_cos_gate(1.0, eng.lib))
+            out.update(shared=shared, narrow=narrow, score=prep_score(shared, narrow))
+            out["selection"] = prep_select(out["score"], max_views)
+        out["timing"] = eng.timing()
+    finally:
+        if engine is None:
+            eng.close()
+    return out
 
 
 def cloud_metrics(rec_xyz, gt_xyz, tolerances=ETH3D_TOLERANCES, max_dist=None, voxel: float = 0.0,

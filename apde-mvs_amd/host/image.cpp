@@ -772,12 +772,39 @@ bool read_bgr8(const std::string &path, Bgr8 &out, std::string &err) {
     return false;
 }
 
+namespace {
+bool write_png_raw(const std::string &path, const std::vector<uint8_t> &raw, int w, int h, uint8_t colour_type);
+}
+
 bool write_png_gray8(const std::string &path, const uint8_t *px, int w, int h) {
     std::vector<uint8_t> raw(((size_t)w + 1) * h);
     for (int r = 0; r < h; ++r) {
         raw[((size_t)w + 1) * r] = 0;  // filter: none
         memcpy(&raw[((size_t)w + 1) * r + 1], px + (size_t)r * w, w);
     }
+    return write_png_raw(path, raw, w, h, 0);
+}
+
+bool write_png_bgr8(const std::string &path, const uint8_t *bgr, int w, int h) {
+    if (w < 1 || h < 1) return false;
+    const size_t stride = 3 * (size_t)w + 1;
+    std::vector<uint8_t> raw(stride * h);
+    for (int r = 0; r < h; ++r) {
+        uint8_t *row = &raw[stride * r];
+        *row++ = 0;  // filter: none
+        const uint8_t *src = bgr + 3 * (size_t)r * w;
+        for (int c = 0; c < w; ++c, src += 3, row += 3) {
+            row[0] = src[2];
+            row[1] = src[1];
+            row[2] = src[0];
+        }
+    }
+    return write_png_raw(path, raw, w, h, 2);
+}
+
+namespace {
+// raw: the filtered scanlines (filter byte + pixels per row)
+bool write_png_raw(const std::string &path, const std::vector<uint8_t> &raw, int w, int h, uint8_t colour_type) {
     uLongf zlen = compressBound((uLong)raw.size());
     std::vector<uint8_t> z(zlen);
     if (compress2(z.data(), &zlen, raw.data(), (uLong)raw.size(), 1) != Z_OK) return false;
@@ -800,12 +827,14 @@ bool write_png_gray8(const std::string &path, const uint8_t *px, int w, int h) {
     std::vector<uint8_t> ihdr;
     put32(ihdr, (uint32_t)w);
     put32(ihdr, (uint32_t)h);
-    ihdr.insert(ihdr.end(), {8, 0, 0, 0, 0});  // 8-bit gray, deflate, adaptive filter, no interlace
+    ihdr.insert(ihdr.end(), {8, colour_type, 0, 0, 0});  // 8-bit gray (0) or RGB (2), deflate, adaptive filter, no interlace
     chunk("IHDR", ihdr);
     chunk("IDAT", z);
     chunk("IEND", {});
+    o.flush();
     return (bool)o;
 }
+}  // namespace
 
 // ----------------------------------------------------------------------------------------------
 // resize

@@ -36,6 +36,8 @@ bool decode_jpeg_bgr(const std::vector<uint8_t> &file, Bgr8 &out, std::string &e
 bool decode_pnm_bgr(const std::vector<uint8_t> &file, Bgr8 &out, std::string &err);
 // cv::imwrite of an 8-bit gray image as PNG (skip.png, APD.cpp:1036-1037).
 bool write_png_gray8(const std::string &path, const uint8_t *px, int w, int h);
+// 8-bit colour PNG (RGB, no alpha) of a BGR-interleaved image; read_bgr8 reads it back bit for bit.
+bool write_png_bgr8(const std::string &path, const uint8_t *bgr, int w, int h);
 // cv::resize INTER_LINEAR on CV_8UC3 (RescaleImageAndCamera, APD.cpp:857); fixed-point path.
 void resize_linear_u8c3(const uint8_t *src, int sw, int sh, uint8_t *dst, int dw, int dh);
 

@@ -8,6 +8,8 @@
 
 #include <algorithm>
 #include <cctype>
+#include <cerrno>
+#include <charconv>
 #include <climits>
 #include <cmath>
 #include <cstdio>
@@ -465,6 +467,491 @@ bool read_pair_file(const std::string &dense, std::vector<Problem> &problems, st
             return false;
         }
         problems.push_back(p);
+    }
+    return true;
+}
+
+// ----------------------------------------------------------------------------------------------
+// COLMAP sparse models
+// ----------------------------------------------------------------------------------------------
+namespace {
+bool slurp(const std::string &path, std::vector<uint8_t> &data, std::string &err) {
+    std::ifstream in(path, std::ios::binary);
+    if (!in) { err = "cannot open " + path; return false; }
+    in.seekg(0, std::ios::end);
+    const std::streamoff n = in.tellg();
+    if (n < 0) { err = "cannot size " + path; return false; }
+    in.seekg(0);
+    data.resize((size_t)n);
+    if (n > 0 && !in.read(reinterpret_cast<char *>(data.data()), n)) { err = "cannot read " + path; return false; }
+    return true;
+}
+
+// the data lines of a COLMAP text file: '#' lines are comments; `keep_empty` keeps blank lines
+// (the 2D-point line of an image may be empty)
+std::vector<std::string> text_lines(const std::vector<uint8_t> &data, bool keep_empty) {
+    std::vector<std::string> lines;
+    size_t i = 0;
+    while (i < data.size()) {
+        size_t j = i;
+        while (j < data.size() && data[j] != '\n') ++j;
+        std::string line(data.begin() + (long)i, data.begin() + (long)j);
+        if (!line.empty() && line.back() == '\r') line.pop_back();
+        size_t k = 0;
+        while (k < line.size() && isspace((unsigned char)line[k])) ++k;
+        const bool blank = k == line.size();
+        if (!(k < line.size() && line[k] == '#') && (keep_empty || !blank)) lines.push_back(line);
+        i = j + 1;
+    }
+    return lines;
+}
+
+std::vector<std::string> split_ws(const std::string &line) {
+    std::vector<std::string> t;
+    size_t i = 0;
+    while (i < line.size()) {
+        while (i < line.size() && isspace((unsigned char)line[i])) ++i;
+        size_t j = i;
+        while (j < line.size() && !isspace((unsigned char)line[j])) ++j;
+        if (j > i) t.push_back(line.substr(i, j - i));
+        i = j;
+    }
+    return t;
+}
+
+bool tok_double(const std::string &s, double &v) {
+    if (s.empty() || s.size() > 64) return false;
+    char *end = nullptr;
+    v = std::strtod(s.c_str(), &end);
+    return end == s.c_str() + s.size() && std::isfinite(v);
+}
+bool tok_int(const std::string &s, long long lo, long long hi, long long &v) {
+    if (s.empty() || s.size() > 24) return false;
+    char *end = nullptr;
+    errno = 0;
+    v = std::strtoll(s.c_str(), &end, 10);
+    return errno == 0 && end == s.c_str() + s.size() && v >= lo && v <= hi;
+}
+
+// little-endian cursor over a binary file
+struct Cursor {
+    const std::vector<uint8_t> &d;
+    size_t pos = 0;
+    size_t left() const { return d.size() - pos; }
+    template <class T> bool get(T &v) {
+        if (left() < sizeof(T)) return false;
+        memcpy(&v, d.data() + pos, sizeof(T));
+        pos += sizeof(T);
+        return true;
+    }
+};
+
+int model_params(const std::string &model) { return model == "SIMPLE_PINHOLE" ? 3 : model == "PINHOLE" ? 4 : 0; }
+
+const char *const kColmapModels[] = {"SIMPLE_PINHOLE", "PINHOLE", "SIMPLE_RADIAL", "RADIAL", "OPENCV", "OPENCV_FISHEYE",
+                                     "FULL_OPENCV", "FOV", "SIMPLE_RADIAL_FISHEYE", "RADIAL_FISHEYE",
+                                     "THIN_PRISM_FISHEYE"};
+
+bool read_cameras(const std::string &path, bool bin, std::vector<ColmapCamera> &cams, std::string &err) {
+    std::vector<uint8_t> data;
+    if (!slurp(path, data, err)) return false;
+    auto fail = [&](const std::string &w) { err = path + ": " + w; return false; };
+    if (bin) {
+        Cursor c{data};
+        uint64_t n = 0;
+        if (!c.get(n)) return fail("truncated header");
+        if (n > c.left() / 48) return fail("camera count " + std::to_string(n) + " exceeds the file");
+        for (uint64_t i = 0; i < n; ++i) {
+            ColmapCamera cam;
+            int32_t model = 0;
+            if (!c.get(cam.id) || !c.get(model) || !c.get(cam.width) || !c.get(cam.height)) return fail("truncated camera");
+            if (model != 0 && model != 1)
+                return fail("unsupported camera model " +
+                            (model >= 2 && model <= 10 ? std::string(kColmapModels[model]) : "id " + std::to_string(model)) +
+                            " (only SIMPLE_PINHOLE and PINHOLE; undistort the images first)");
+            cam.model = kColmapModels[model];
+            cam.params.resize((size_t)model_params(cam.model));
+            for (double &p : cam.params)
+                if (!c.get(p) || !std::isfinite(p)) return fail("truncated or non-finite camera parameters");
+            cams.push_back(cam);
+        }
+        if (c.left()) return fail("bytes after the last camera");
+    } else {
+        for (const std::string &line : text_lines(data, false)) {
+            const std::vector<std::string> t = split_ws(line);
+            ColmapCamera cam;
+            long long id, w, h;
+            if (t.size() < 4 || !tok_int(t[0], 0, UINT32_MAX, id) || !tok_int(t[2], 0, INT32_MAX, w) ||
+                !tok_int(t[3], 0, INT32_MAX, h))
+                return fail("bad camera line '" + line.substr(0, 80) + "'");
+            cam.id = (uint32_t)id;
+            cam.model = t[1];
+            cam.width = (uint64_t)w;
+            cam.height = (uint64_t)h;
+            const int np = model_params(cam.model);
+            if (!np)
+                return fail("unsupported camera model " + cam.model.substr(0, 40) +
+                            " (only SIMPLE_PINHOLE and PINHOLE; undistort the images first)");
+            if ((int)t.size() != 4 + np) return fail("camera " + t[0] + ": wrong number of parameters");
+            cam.params.resize((size_t)np);
+            for (int k = 0; k < np; ++k)
+                if (!tok_double(t[4 + (size_t)k], cam.params[(size_t)k])) return fail("camera " + t[0] + ": bad parameter");
+            cams.push_back(cam);
+        }
+    }
+    for (const ColmapCamera &cam : cams)
+        if (cam.width < 1 || cam.height < 1 || cam.width > 65536 || cam.height > 65536)
+            return fail("camera " + std::to_string(cam.id) + ": size out of range");
+    if (cams.empty()) return fail("no camera");
+    return true;
+}
+
+bool read_images(const std::string &path, bool bin, std::vector<ColmapImage> &images, std::string &err) {
+    std::vector<uint8_t> data;
+    if (!slurp(path, data, err)) return false;
+    auto fail = [&](const std::string &w) { err = path + ": " + w; return false; };
+    if (bin) {
+        Cursor c{data};
+        uint64_t n = 0;
+        if (!c.get(n)) return fail("truncated header");
+        if (n > c.left() / 73) return fail("image count " + std::to_string(n) + " exceeds the file");
+        images.reserve((size_t)n);
+        for (uint64_t i = 0; i < n; ++i) {
+            ColmapImage im;
+            if (!c.get(im.id)) return fail("truncated image");
+            for (double &v : im.q) if (!c.get(v) || !std::isfinite(v)) return fail("truncated or non-finite pose");
+            for (double &v : im.t) if (!c.get(v) || !std::isfinite(v)) return fail("truncated or non-finite pose");
+            if (!c.get(im.camera_id)) return fail("truncated image");
+            size_t e = c.pos;
+            while (e < data.size() && data[e] != 0) ++e;
+            if (e == data.size() || e - c.pos > 4096) return fail("unterminated image name");
+            im.name.assign(data.begin() + (long)c.pos, data.begin() + (long)e);
+            c.pos = e + 1;
+            uint64_t np = 0;
+            if (!c.get(np)) return fail("truncated image");
+            if (np > c.left() / 24) return fail("2D point count " + std::to_string(np) + " exceeds the file");
+            im.xy.resize(2 * (size_t)np);
+            im.point_ids.resize((size_t)np);
+            for (size_t k = 0; k < (size_t)np; ++k) {
+                c.get(im.xy[2 * k]);
+                c.get(im.xy[2 * k + 1]);
+                c.get(im.point_ids[k]);
+                if (im.point_ids[k] < -1) return fail("image " + std::to_string(im.id) + ": bad point id");
+            }
+            images.push_back(std::move(im));
+        }
+        if (c.left()) return fail("bytes after the last image");
+    } else {
+        const std::vector<std::string> lines = text_lines(data, true);
+        size_t li = 0;
+        while (li < lines.size()) {
+            const std::vector<std::string> t = split_ws(lines[li]);
+            if (t.empty()) { ++li; continue; }  // blank lines between images
+            ColmapImage im;
+            long long id, cam;
+            if (t.size() != 10 || !tok_int(t[0], 0, UINT32_MAX, id) || !tok_int(t[8], 0, UINT32_MAX, cam))
+                return fail("bad image line '" + lines[li].substr(0, 80) + "'");
+            for (int k = 0; k < 4; ++k) if (!tok_double(t[1 + (size_t)k], im.q[k])) return fail("image " + t[0] + ": bad pose");
+            for (int k = 0; k < 3; ++k) if (!tok_double(t[5 + (size_t)k], im.t[k])) return fail("image " + t[0] + ": bad pose");
+            im.id = (uint32_t)id;
+            im.camera_id = (uint32_t)cam;
+            im.name = t[9];
+            if (li + 1 >= lines.size()) return fail("image " + t[0] + ": missing 2D-point line");
+            const std::vector<std::string> p = split_ws(lines[li + 1]);
+            if (p.size() % 3) return fail("image " + t[0] + ": the 2D-point line is not made of triples");
+            im.xy.resize(p.size() / 3 * 2);
+            im.point_ids.resize(p.size() / 3);
+            for (size_t k = 0; k < p.size() / 3; ++k) {
+                long long pid;
+                if (!tok_double(p[3 * k], im.xy[2 * k]) || !tok_double(p[3 * k + 1], im.xy[2 * k + 1]) ||
+                    !tok_int(p[3 * k + 2], -1, LLONG_MAX, pid))
+                    return fail("image " + t[0] + ": bad 2D point '" + p[3 * k + 2].substr(0, 40) + "'");
+                im.point_ids[k] = pid;
+            }
+            images.push_back(std::move(im));
+            li += 2;
+        }
+    }
+    if (images.empty()) return fail("no image");
+    std::sort(images.begin(), images.end(), [](const ColmapImage &a, const ColmapImage &b) { return a.id < b.id; });
+    for (size_t i = 1; i < images.size(); ++i)
+        if (images[i].id == images[i - 1].id) return fail("duplicate image id " + std::to_string(images[i].id));
+    for (const ColmapImage &im : images)
+        if (im.name.empty() || im.name[0] == '/' || im.name.find("..") != std::string::npos)
+            return fail("image " + std::to_string(im.id) + ": unusable name");
+    return true;
+}
+
+bool read_points(const std::string &path, bool bin, std::vector<int64_t> &ids, std::vector<double> &xyz, std::string &err) {
+    std::vector<uint8_t> data;
+    if (!slurp(path, data, err)) return false;
+    auto fail = [&](const std::string &w) { err = path + ": " + w; return false; };
+    if (bin) {
+        Cursor c{data};
+        uint64_t n = 0;
+        if (!c.get(n)) return fail("truncated header");
+        if (n > c.left() / 51) return fail("point count " + std::to_string(n) + " exceeds the file");
+        ids.reserve((size_t)n);
+        xyz.reserve(3 * (size_t)n);
+        for (uint64_t i = 0; i < n; ++i) {
+            uint64_t id = 0, track = 0;
+            double p[3], e;
+            uint8_t rgb[3];
+            if (!c.get(id) || !c.get(p[0]) || !c.get(p[1]) || !c.get(p[2]) || !c.get(rgb[0]) || !c.get(rgb[1]) ||
+                !c.get(rgb[2]) || !c.get(e) || !c.get(track))
+                return fail("truncated point");
+            if (id > (uint64_t)INT64_MAX) return fail("point id out of range");
+            if (!std::isfinite(p[0]) || !std::isfinite(p[1]) || !std::isfinite(p[2])) return fail("non-finite point");
+            if (track > c.left() / 8) return fail("track length " + std::to_string(track) + " exceeds the file");
+            c.pos += 8 * (size_t)track;
+            ids.push_back((int64_t)id);
+            xyz.insert(xyz.end(), p, p + 3);
+        }
+        if (c.left()) return fail("bytes after the last point");
+    } else {
+        for (const std::string &line : text_lines(data, false)) {
+            const std::vector<std::string> t = split_ws(line);
+            long long id;
+            double p[3];
+            if (t.size() < 8 || t.size() % 2 || !tok_int(t[0], 0, LLONG_MAX, id) || !tok_double(t[1], p[0]) ||
+                !tok_double(t[2], p[1]) || !tok_double(t[3], p[2]))
+                return fail("bad point line '" + line.substr(0, 80) + "'");
+            ids.push_back(id);
+            xyz.insert(xyz.end(), p, p + 3);
+        }
+    }
+    return true;
+}
+}  // namespace
+
+bool read_colmap_model(const std::string &dir, const std::string &ext, ColmapModel &m, std::string &err) {
+    m = ColmapModel();
+    if (ext != ".txt" && ext != ".bin") { err = "model extension must be .txt or .bin, not '" + ext + "'"; return false; }
+    const bool bin = ext == ".bin";
+    if (!read_cameras(dir + "/cameras" + ext, bin, m.cameras, err) ||
+        !read_images(dir + "/images" + ext, bin, m.images, err) ||
+        !read_points(dir + "/points3D" + ext, bin, m.point_ids, m.xyz, err))
+        return false;
+    std::map<uint32_t, int> cams;
+    for (const ColmapCamera &c : m.cameras)
+        if (!cams.emplace(c.id, 0).second) { err = dir + ": duplicate camera id " + std::to_string(c.id); return false; }
+    for (const ColmapImage &im : m.images)
+        if (!cams.count(im.camera_id)) {
+            err = dir + ": image " + std::to_string(im.id) + " names camera " + std::to_string(im.camera_id) + ", which is missing";
+            return false;
+        }
+    return true;
+}
+
+bool colmap_prep_arrays(const ColmapModel &m, PrepArrays &a, std::string &err) {
+    a = PrepArrays();
+    std::vector<std::pair<int64_t, int32_t>> index(m.point_ids.size());
+    if (m.point_ids.size() > (size_t)INT32_MAX) { err = "more than INT32_MAX points"; return false; }
+    for (size_t k = 0; k < m.point_ids.size(); ++k) index[k] = {m.point_ids[k], (int32_t)k};
+    std::sort(index.begin(), index.end());
+    for (size_t k = 1; k < index.size(); ++k)
+        if (index[k].first == index[k - 1].first) { err = "duplicate point id " + std::to_string(index[k].first); return false; }
+    a.obs_offset.push_back(0);
+    for (const ColmapImage &im : m.images) {
+        const double w = im.q[0], x = im.q[1], y = im.q[2], z = im.q[3];
+        const double R[9] = {(1 - 2 * (y * y)) - 2 * (z * z), (2 * x) * y - (2 * w) * z, (2 * z) * x + (2 * w) * y,
+                             (2 * x) * y + (2 * w) * z, (1 - 2 * (x * x)) - 2 * (z * z), (2 * y) * z - (2 * w) * x,
+                             (2 * z) * x - (2 * w) * y, (2 * y) * z + (2 * w) * x, (1 - 2 * (x * x)) - 2 * (y * y)};
+        a.rot.insert(a.rot.end(), R, R + 9);
+        a.trans.insert(a.trans.end(), im.t, im.t + 3);
+        for (int k = 0; k < 3; ++k) a.centres.push_back(-((R[k] * im.t[0] + R[3 + k] * im.t[1]) + R[6 + k] * im.t[2]));
+        for (int64_t pid : im.point_ids) {
+            if (pid == -1) continue;
+            auto it = std::lower_bound(index.begin(), index.end(), std::make_pair(pid, (int32_t)INT32_MIN));
+            if (it == index.end() || it->first != pid) {
+                err = "image " + std::to_string(im.id) + " names point " + std::to_string(pid) + ", which points3D lacks";
+                return false;
+            }
+            a.obs_point.push_back(it->second);
+        }
+        if (a.obs_point.size() > (size_t)INT32_MAX) { err = "more than INT32_MAX observations"; return false; }
+        a.obs_offset.push_back((int64_t)a.obs_point.size());
+    }
+    return true;
+}
+
+ViewSelection select_sequential(int n, int k) {
+    ViewSelection sel((size_t)std::max(n, 0));
+    const long lim = std::min<long>((long)n - 1, 2L * k);
+    for (int i = 0; i < n; ++i) {
+        std::vector<std::pair<int, int>> nb;
+        for (int off = 1; off <= k; ++off)
+            for (int dir = -1; dir <= 1; dir += 2) {
+                const long j = (long)i + (long)dir * off;
+                if (j >= 0 && j < n) nb.push_back({(int)j, k + 1 - off});
+            }
+        std::stable_sort(nb.begin(), nb.end(), [i](const std::pair<int, int> &a, const std::pair<int, int> &b) {
+            if (a.second != b.second) return a.second > b.second;
+            return std::abs(a.first - i) < std::abs(b.first - i);
+        });
+        if ((long)nb.size() > lim) nb.resize((size_t)std::max(lim, 0L));
+        sel[(size_t)i] = nb;
+    }
+    return sel;
+}
+
+ViewSelection select_scored(int n, const uint32_t *shared, const uint32_t *narrow, int max_views) {
+    ViewSelection sel((size_t)std::max(n, 0));
+    const int take = std::max(0, std::min(max_views, n - 1));
+    std::vector<std::pair<int64_t, int>> cand;
+    for (int i = 0; i < n; ++i) {
+        cand.clear();
+        for (int j = 0; j < n; ++j) {
+            if (j == i) continue;
+            const uint64_t s = shared[(size_t)i * n + j], nar = narrow[(size_t)i * n + j];
+            const int64_t score = nar >= 3 * s / 4 + 1 ? 0 : (int64_t)s;
+            cand.push_back({-score, j});
+        }
+        std::partial_sort(cand.begin(), cand.begin() + take, cand.end());
+        for (int k = 0; k < take; ++k) sel[(size_t)i].push_back({cand[(size_t)k].second, (int)-cand[(size_t)k].first});
+    }
+    return sel;
+}
+
+std::string shortest_double(double v) {
+    char buf[40];
+    const std::to_chars_result r = std::to_chars(buf, buf + sizeof buf, v);  // shortest round-trip form
+    return std::string(buf, r.ptr);
+}
+
+bool write_cam_txt(const std::string &path, const double R[9], const double t[3], const double K[9], double depth_min,
+                   double interval, double depth_num, double depth_max) {
+    std::ofstream o(path);
+    if (!o) return false;
+    o << "extrinsic\n";
+    for (int r = 0; r < 3; ++r)
+        o << shortest_double(R[3 * r]) << ' ' << shortest_double(R[3 * r + 1]) << ' ' << shortest_double(R[3 * r + 2])
+          << ' ' << shortest_double(t[r]) << " \n";
+    o << "0.0 0.0 0.0 1.0 \n\nintrinsic\n";
+    for (int r = 0; r < 3; ++r)
+        o << shortest_double(K[3 * r]) << ' ' << shortest_double(K[3 * r + 1]) << ' ' << shortest_double(K[3 * r + 2])
+          << " \n";
+    char buf[256];
+    snprintf(buf, sizeof buf, "\n%f %f %f %f\n", depth_min, interval, depth_num, depth_max);
+    o << buf;
+    o.flush();
+    return (bool)o;
+}
+
+bool write_pair_txt(const std::string &path, const ViewSelection &sel) {
+    std::ofstream o(path);
+    if (!o) return false;
+    o << sel.size() << '\n';
+    for (size_t i = 0; i < sel.size(); ++i) {
+        o << i << '\n' << sel[i].size() << ' ';
+        for (const auto &js : sel[i]) o << js.first << ' ' << js.second << ' ';
+        o << '\n';
+    }
+    o.flush();
+    return (bool)o;
+}
+
+bool write_colmap_cameras_txt(const std::string &path, const std::vector<ColmapCamera> &cams) {
+    std::ofstream o(path);
+    if (!o) return false;
+    o << "# Camera list with one line of data per camera:\n#   CAMERA_ID, MODEL, WIDTH, HEIGHT, PARAMS[]\n"
+      << "# Number of cameras: " << cams.size() << '\n';
+    for (const ColmapCamera &c : cams) {
+        o << c.id << ' ' << c.model << ' ' << c.width << ' ' << c.height;
+        for (double p : c.params) o << ' ' << shortest_double(p);
+        o << '\n';
+    }
+    o.flush();
+    return (bool)o;
+}
+
+bool write_colmap_images_txt(const std::string &path, const std::vector<ColmapImage> &images) {
+    std::ofstream o(path);
+    if (!o) return false;
+    o << "# Image list with two lines of data per image:\n#   IMAGE_ID, QW, QX, QY, QZ, TX, TY, TZ, CAMERA_ID, NAME\n"
+      << "#   POINTS2D[] as (X, Y, POINT3D_ID)\n# Number of images: " << images.size() << '\n';
+    for (const ColmapImage &im : images) {
+        o << im.id;
+        for (double v : im.q) o << ' ' << shortest_double(v);
+        for (double v : im.t) o << ' ' << shortest_double(v);
+        o << ' ' << im.camera_id << ' ' << im.name << '\n';
+        for (size_t k = 0; k < im.point_ids.size(); ++k)
+            o << (k ? " " : "") << shortest_double(im.xy[2 * k]) << ' ' << shortest_double(im.xy[2 * k + 1]) << ' '
+              << im.point_ids[k];
+        o << '\n';
+    }
+    o.flush();
+    return (bool)o;
+}
+
+bool copy_file(const std::string &from, const std::string &to) {
+    std::ifstream in(from, std::ios::binary);
+    if (!in) return false;
+    std::ofstream o(to, std::ios::binary);
+    if (!o) return false;
+    o << in.rdbuf();
+    o.flush();
+    return (bool)o && !in.bad();
+}
+
+bool scan_image_sizes(const std::string &image_dir, const std::vector<std::string> &names, std::vector<int> &widths,
+                      std::vector<int> &heights, std::string &err) {
+    widths.assign(names.size(), 0);
+    heights.assign(names.size(), 0);
+    for (size_t i = 0; i < names.size(); ++i) {
+        Bgr8 img;
+        if (!read_bgr8(image_dir + "/" + names[i], img, err)) return false;
+        if (img.width < 1 || img.height < 1) { err = "empty image " + names[i]; return false; }
+        widths[i] = img.width;
+        heights[i] = img.height;
+    }
+    return true;
+}
+
+bool convert_scan_images(const std::string &image_dir, const std::vector<std::string> &names,
+                         const std::vector<int> &widths, const std::vector<int> &heights, double scale,
+                         const std::string &out_dir, std::vector<std::string> &out_names, int &out_w, int &out_h,
+                         int &copied, std::string &err) {
+    out_names.clear();
+    copied = 0;
+    if (names.empty() || widths.size() != names.size() || heights.size() != names.size() || !(scale > 0)) {
+        err = "convert_scan_images: bad arguments";
+        return false;
+    }
+    const int max_w = *std::max_element(widths.begin(), widths.end());
+    const int max_h = *std::max_element(heights.begin(), heights.end());
+    out_w = (int)((double)max_w / scale);
+    out_h = (int)((double)max_h / scale);
+    if (out_w < 1 || out_h < 1) { err = "the scale factor leaves no pixels"; return false; }
+    for (size_t i = 0; i < names.size(); ++i) {
+        const std::string src = image_dir + "/" + names[i];
+        std::string e;
+        const size_t dot = names[i].rfind('.'), slash = names[i].rfind('/');
+        if (dot != std::string::npos && (slash == std::string::npos || dot > slash)) e = names[i].substr(dot);
+        for (char &c : e) c = (char)tolower((unsigned char)c);
+        const bool as_is = scale == 1.0 && widths[i] == max_w && heights[i] == max_h &&
+                           (e == ".jpg" || e == ".jpeg" || e == ".png");
+        const std::string name = format_index((int)i) + (as_is ? e : ".png");
+        for (const char *stale : {".jpg", ".jpeg", ".png"})
+            if (name != format_index((int)i) + stale) std::remove((out_dir + "/" + format_index((int)i) + stale).c_str());
+        if (as_is) {
+            if (!copy_file(src, out_dir + "/" + name)) { err = "cannot copy " + src + " to " + out_dir + "/" + name; return false; }
+            ++copied;
+        } else {
+            Bgr8 img;
+            if (!read_bgr8(src, img, err)) return false;
+            if (img.width != widths[i] || img.height != heights[i]) { err = src + " changed size"; return false; }
+            std::vector<uint8_t> pad(3 * (size_t)max_w * max_h, 0);
+            for (int r = 0; r < img.height; ++r)
+                memcpy(&pad[3 * (size_t)r * max_w], &img.px[3 * (size_t)r * img.width], 3 * (size_t)img.width);
+            std::vector<uint8_t> out(3 * (size_t)out_w * out_h);
+            resize_nearest(pad.data(), max_w, max_h, out.data(), out_w, out_h, 3);
+            if (!write_png_bgr8(out_dir + "/" + name, out.data(), out_w, out_h)) {
+                err = "cannot write " + out_dir + "/" + name;
+                return false;
+            }
+        }
+        out_names.push_back(name);
     }
     return true;
 }

@@ -123,6 +123,73 @@ bool read_mlp(const std::string &path, std::vector<MlpMesh> &meshes, std::string
 // right and rounded once to float. origin = the translation column rounded to float: the scanner.
 void mlp_to_world(const MlpMesh &m, std::vector<float> &xyz, float origin[3]);
 
+// ---- COLMAP sparse models (apd_prepare; the reference's tools/colmap2mvsnet.py) ---------------------
+struct ColmapCamera {
+    uint32_t id = 0;
+    std::string model;  // SIMPLE_PINHOLE or PINHOLE
+    uint64_t width = 0, height = 0;
+    std::vector<double> params;  // f cx cy | fx fy cx cy
+};
+struct ColmapImage {
+    uint32_t id = 0, camera_id = 0;
+    double q[4] = {1, 0, 0, 0}, t[3] = {0, 0, 0};
+    std::string name;
+    std::vector<double> xy;          // 2 per 2D point
+    std::vector<int64_t> point_ids;  // -1: no 3D point
+};
+struct ColmapModel {
+    std::vector<ColmapCamera> cameras;
+    std::vector<ColmapImage> images;  // ascending id: index = the new image number
+    std::vector<int64_t> point_ids;   // in file order
+    std::vector<double> xyz;          // 3 per point
+};
+// cameras, images and points3D of `dir` with extension ".txt" or ".bin". Only SIMPLE_PINHOLE and
+// PINHOLE cameras are accepted, as in the reference. Every count is bounded by the file's size before
+// anything is allocated; truncated or garbled files, non-numeric tokens, non-finite numbers, duplicate
+// ids and an image whose camera is missing are rejected with a message in `err`.
+bool read_colmap_model(const std::string &dir, const std::string &ext, ColmapModel &m, std::string &err);
+
+// The arrays of apd_prep_set_model (include/apd_prep.h): R by the contract's qvec formula, centres,
+// and the observations as indices into the point array, grouped by image. A point id an image names
+// that points3D lacks is an error.
+struct PrepArrays {
+    std::vector<double> rot, trans, centres;
+    std::vector<int64_t> obs_offset;
+    std::vector<int32_t> obs_point;
+};
+bool colmap_prep_arrays(const ColmapModel &m, PrepArrays &a, std::string &err);
+
+typedef std::vector<std::vector<std::pair<int, int>>> ViewSelection;  // per view: (source, score)
+// tools/colmap2mvsnet.py:453-468
+ViewSelection select_sequential(int n, int k);
+// score = shared, 0 where narrow >= floor(3*shared/4) + 1; per view the first min(max_views, n-1) of
+// j != i by (score descending, j ascending), zero scores included
+ViewSelection select_scored(int n, const uint32_t *shared, const uint32_t *narrow, int max_views);
+
+// shortest decimal that parses back to the same double
+std::string shortest_double(double v);
+// cam.txt in the reference's layout (:495-507): extrinsic 4x4, intrinsic 3x3 (shortest round-trip
+// decimals), then "%f %f %f %f" of depth_min, interval, depth_num, depth_max
+bool write_cam_txt(const std::string &path, const double R[9], const double t[3], const double K[9],
+                   double depth_min, double interval, double depth_num, double depth_max);
+bool write_pair_txt(const std::string &path, const ViewSelection &sel);  // :508-514
+bool write_colmap_cameras_txt(const std::string &path, const std::vector<ColmapCamera> &cams);
+bool write_colmap_images_txt(const std::string &path, const std::vector<ColmapImage> &images);
+bool copy_file(const std::string &from, const std::string &to);
+// The images of a scan (:516-536). scan_image_sizes decodes every image_dir/name for its size.
+// convert_scan_images writes out_dir/%08d<ext>: with scale == 1 and an image of the largest size, a
+// source named .jpg/.jpeg/.png (any case) is copied byte for byte under its lower-cased extension;
+// otherwise it is decoded, padded bottom and right with zeros to the largest size, resized to
+// (int(W/scale), int(H/scale)) by resize_nearest and written as 8-bit colour PNG (there is no JPEG
+// encoder here: lossless, where the reference recompresses). Files %08d.{jpg,jpeg,png} of another
+// extension left by an earlier run are removed, so every index has one image.
+bool scan_image_sizes(const std::string &image_dir, const std::vector<std::string> &names, std::vector<int> &widths,
+                      std::vector<int> &heights, std::string &err);
+bool convert_scan_images(const std::string &image_dir, const std::vector<std::string> &names,
+                         const std::vector<int> &widths, const std::vector<int> &heights, double scale,
+                         const std::string &out_dir, std::vector<std::string> &out_names, int &out_w, int &out_h,
+                         int &copied, std::string &err);
+
 std::string format_index(int id);  // ToFormatIndex: %08d
 bool file_exists(const std::string &p);
 bool make_dir(const std::string &p);
