@@ -239,6 +239,14 @@ EVAL_EXPORTS = ["apd_eval_create", "apd_eval_destroy", "apd_eval_last_error", "a
 # include/apd_prep.h
 PREP_EXPORTS = ["apd_prep_create", "apd_prep_destroy", "apd_prep_last_error", "apd_prep_set_model",
                 "apd_prep_pair_counts", "apd_prep_depth_ranks", "apd_prep_get_timing", "apd_prep_cos_gate"]
+# include/apd_prep.h, the undistortion entries: a list of their own, because PREP_EXPORTS is pinned at
+# the eight entries of scan preparation proper (tests/test_prep_host.py)
+PREP_UNDISTORT_EXPORTS = ["apd_prep_undistort_bgr8", "apd_prep_get_undistort_timing", "apd_prep_undistort_bgr8_host",
+                          "apd_prep_atan_c", "apd_prep_undistort_xy"]
+# COLMAP's camera model ids and parameter counts (FOV, 7, is not supported)
+PREP_CAMERA_MODELS = {"SIMPLE_PINHOLE": (0, 3), "PINHOLE": (1, 4), "SIMPLE_RADIAL": (2, 4), "RADIAL": (3, 5),
+                      "OPENCV": (4, 8), "OPENCV_FISHEYE": (5, 8), "FULL_OPENCV": (6, 12),
+                      "SIMPLE_RADIAL_FISHEYE": (8, 4), "RADIAL_FISHEYE": (9, 5), "THIN_PRISM_FISHEYE": (10, 12)}
 PREP_MAX_IMAGES = 16384
 PREP_ATOMICS_DEFAULT, PREP_ATOMICS_GLOBAL, PREP_ATOMICS_LDS = 0, 1, 2
 
@@ -397,6 +405,20 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
                                         C.POINTER(C.c_double), C.POINTER(C.c_double)]
     lib.apd_prep_cos_gate.restype = C.c_double
     lib.apd_prep_cos_gate.argtypes = [C.c_double]
+    lib.apd_prep_undistort_bgr8.restype = C.c_int32
+    lib.apd_prep_undistort_bgr8.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
+                                            C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
+    lib.apd_prep_get_undistort_timing.restype = C.c_int32
+    lib.apd_prep_get_undistort_timing.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                                  C.POINTER(C.c_double)]
+    lib.apd_prep_undistort_bgr8_host.restype = C.c_int32
+    lib.apd_prep_undistort_bgr8_host.argtypes = [C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
+                                                 C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
+    lib.apd_prep_atan_c.restype = C.c_double
+    lib.apd_prep_atan_c.argtypes = [C.c_double]
+    lib.apd_prep_undistort_xy.restype = C.c_int32
+    lib.apd_prep_undistort_xy.argtypes = [C.c_int32, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p,
+                                          C.POINTER(C.c_int64)]
     return lib
 
 
@@ -728,6 +750,57 @@ def prep_cos_gate(degrees: float = 1.0, lib: Optional[C.CDLL] = None) -> float:
     return float((lib or load_library()).apd_prep_cos_gate(float(degrees)))
 
 
+def prep_model_id(model) -> int:
+    """COLMAP's id of a camera model given by name or id."""
+    return PREP_CAMERA_MODELS[model][0] if isinstance(model, str) else int(model)
+
+
+def prep_pinhole_K(model, params):
+    """[fx, fy, cx, cy] of a camera's parameters (fx = fy = f for the f cx cy models)."""
+    p = [float(v) for v in params]
+    return [p[0], p[0], p[1], p[2]] if prep_model_id(model) in (0, 2, 3, 8, 9) else p[:4]
+
+
+def _undistort_args(bgr, model, params, out_K, out_size):
+    src = np.ascontiguousarray(bgr, np.uint8)
+    if src.ndim != 3 or src.shape[2] != 3:
+        raise ValueError("bgr is (h, w, 3) uint8")
+    p = np.ascontiguousarray(params, np.float64).reshape(-1)
+    K = np.ascontiguousarray(prep_pinhole_K(model, p) if out_K is None else out_K, np.float64).reshape(-1)
+    if len(K) != 4:
+        raise ValueError("out_K is fx, fy, cx, cy")
+    ow, oh = (src.shape[1], src.shape[0]) if out_size is None else (int(out_size[0]), int(out_size[1]))
+    return src, p, K, ow, oh
+
+
+def prep_undistort_host(bgr, model, params, out_K=None, out_size=None, lib: Optional[C.CDLL] = None) -> np.ndarray:
+    """apd_prep_undistort_bgr8_host: the warp of include/apd_prep.h on the CPU. bgr (h, w, 3) uint8;
+    out_K [fx, fy, cx, cy] (default: the source camera's); out_size (w, h) (default: the source's)."""
+    src, p, K, ow, oh = _undistort_args(bgr, model, params, out_K, out_size)
+    dst = np.empty((max(oh, 0), max(ow, 0), 3), np.uint8)
+    st = (lib or load_library()).apd_prep_undistort_bgr8_host(prep_model_id(model), p.ctypes.data, len(p), src.shape[1],
+                                                              src.shape[0], src.ctypes.data, K.ctypes.data, ow, oh,
+                                                              dst.ctypes.data)
+    if st != 0:
+        raise ApdError(f"apd_prep_undistort_bgr8_host -> {STATUS.get(st, st)}")
+    return dst
+
+
+def prep_undistort_xy(xy, model, params, lib: Optional[C.CDLL] = None):
+    """apd_prep_undistort_xy: (n, 2) distorted pixel coordinates -> ((n, 2) pinhole pixel coordinates with
+    (-1, -1) where Newton's method did not converge, the number of those)."""
+    pts = np.ascontiguousarray(xy, np.float64).reshape(-1, 2)
+    p = np.ascontiguousarray(params, np.float64).reshape(-1)
+    out = np.empty_like(pts)
+    bad = C.c_int64(0)
+    st = (lib or load_library()).apd_prep_undistort_xy(prep_model_id(model), p.ctypes.data, len(p), len(pts),
+                                                       pts.ctypes.data if len(pts) else None,
+                                                       out.ctypes.data if len(pts) else None, C.byref(bad))
+    if st != 0:
+        raise ApdError(f"apd_prep_undistort_xy -> {STATUS.get(st, st)}")
+    return out, int(bad.value)
+
+
 class PrepEngine:
     """One apd_prep_ctx (include/apd_prep.h): pair counts by tracks and per-image depth order
     statistics of a sparse model. All arrays are numpy, in the layout of apd_prep_set_model."""
@@ -786,6 +859,23 @@ class PrepEngine:
         self._check(self.lib.apd_prep_get_timing(self.ctx, C.byref(a), C.byref(b), C.byref(r), C.byref(c)),
                     "apd_prep_get_timing")
         return {"tracks_ms": a.value, "pairs_ms": b.value, "records_ms": r.value, "ranks_ms": c.value}
+
+    def undistort(self, bgr, model, params, out_K=None, out_size=None) -> np.ndarray:
+        """apd_prep_undistort_bgr8: bgr (h, w, 3) uint8 taken with camera `model` (name or COLMAP id) and
+        `params` -> the (out_h, out_w, 3) image of the pinhole camera out_K = [fx, fy, cx, cy] (default: the
+        source camera's) of out_size = (w, h) (default: the source's). Needs no model."""
+        src, p, K, ow, oh = _undistort_args(bgr, model, params, out_K, out_size)
+        dst = np.empty((max(oh, 0), max(ow, 0), 3), np.uint8)
+        self._check(self.lib.apd_prep_undistort_bgr8(self.ctx, prep_model_id(model), p.ctypes.data, len(p), src.shape[1],
+                                                     src.shape[0], src.ctypes.data, K.ctypes.data, ow, oh,
+                                                     dst.ctypes.data), "apd_prep_undistort_bgr8")
+        return dst
+
+    def undistort_timing(self) -> dict:
+        a, b, c = C.c_double(), C.c_double(), C.c_double()
+        self._check(self.lib.apd_prep_get_undistort_timing(self.ctx, C.byref(a), C.byref(b), C.byref(c)),
+                    "apd_prep_get_undistort_timing")
+        return {"upload_ms": a.value, "kernel_ms": b.value, "download_ms": c.value}
 
     def close(self):
         if self.ctx:

@@ -9,6 +9,8 @@
 //               index once and then steps (a, b) forward. AGG: the records of a workgroup's tile are
 //               summed in an LDS hash table keyed by (a, b) before one global atomic per distinct pair.
 // Depth ranks:  k_pr_depth_keys -> rocprim segmented radix sort -> k_pr_pick
+// Undistortion: k_pr_undistort<MODEL>: one output pixel per lane in 64 x 4 tiles, the arithmetic of
+//               apd_undistort.h; the camera travels in the kernel arguments.
 #include <hip/hip_runtime.h>
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
@@ -24,6 +26,7 @@
 #include <vector>
 
 #include "../../include/apd_prep.h"
+#include "apd_undistort.h"
 
 namespace {
 
@@ -276,6 +279,24 @@ __global__ void __launch_bounds__(BLOCK) k_pr_pick(const int64_t *__restrict__ o
     z_at[e] = z;
 }
 
+// A workgroup is 4 rows of 64 pixels: a wave stores one run of 192 bytes, and the sources of a
+// workgroup's pixels lie close together in the source image.
+constexpr int UD_TILE_W = 64, UD_TILE_H = 4;
+
+template <int M>
+__global__ void __launch_bounds__(UD_TILE_W *UD_TILE_H) k_pr_undistort(const apd_ud::Warp W) {
+    const int x = blockIdx.x * UD_TILE_W + threadIdx.x;
+    const int y = blockIdx.y * UD_TILE_H + threadIdx.y;
+    if (x >= W.ow || y >= W.oh) return;
+    apd_ud::warp_pixel<M>(W, x, y);
+}
+
+template <int M>
+void launch_undistort(const apd_ud::Warp &W, hipStream_t s) {
+    const dim3 grid((unsigned)((W.ow + UD_TILE_W - 1) / UD_TILE_W), (unsigned)((W.oh + UD_TILE_H - 1) / UD_TILE_H));
+    hipLaunchKernelGGL(k_pr_undistort<M>, grid, dim3(UD_TILE_W, UD_TILE_H), 0, s, W);
+}
+
 struct Buf {
     void *p = nullptr;
     size_t bytes = 0;
@@ -297,6 +318,9 @@ struct apd_prep_ctx {
     // pair counts and depth ranks
     Buf m_shared, m_narrow, z_keys, z_sorted, frac, z_at;
     Buf tmp;
+    // undistortion: the source and the warped image
+    Buf ud_src, ud_dst;
+    double ud_upload_ms = 0.0, ud_kernel_ms = 0.0, ud_download_ms = 0.0;
     bool has_model = false;
     int n_images = 0, n_points = 0, n_obs = 0, n_tracks = 0;
     uint64_t total = 0;
@@ -378,7 +402,7 @@ void apd_prep_destroy(apd_prep_ctx *ctx) {
     for (Buf *b : {&ctx->rot, &ctx->trans, &ctx->centres, &ctx->xyz, &ctx->obs_off, &ctx->obs_point, &ctx->keys,
                    &ctx->keys_s, &ctx->head_u, &ctx->head_p, &ctx->pos_u, &ctx->pos_p, &ctx->u_image, &ctx->t_start,
                    &ctx->t_point, &ctx->rec, &ctx->rec_off, &ctx->counts, &ctx->m_shared, &ctx->m_narrow, &ctx->z_keys,
-                   &ctx->z_sorted, &ctx->frac, &ctx->z_at, &ctx->tmp})
+                   &ctx->z_sorted, &ctx->frac, &ctx->z_at, &ctx->tmp, &ctx->ud_src, &ctx->ud_dst})
         if (b->p) (void)hipFree(b->p);
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
     if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
@@ -625,6 +649,58 @@ int32_t apd_prep_get_timing(apd_prep_ctx *ctx, double *tracks_ms, double *pairs_
     if (pairs_ms) *pairs_ms = ctx->pairs_ms;
     if (records_ms) *records_ms = ctx->records_ms;
     if (ranks_ms) *ranks_ms = ctx->ranks_ms;
+    return APD_OK;
+}
+
+int32_t apd_prep_undistort_bgr8(apd_prep_ctx *ctx, int32_t model_id, const double *params, int32_t n_params,
+                                int32_t src_w, int32_t src_h, const uint8_t *src, const double *out_K, int32_t out_w,
+                                int32_t out_h, uint8_t *dst) {
+    if (!ctx) return APD_EINVAL;
+    if (const char *what = apd_ud::check_warp(model_id, params, n_params, src_w, src_h, src, out_K, out_w, out_h, dst))
+        return fail(ctx, std::string("apd_prep_undistort_bgr8: ") + what);
+    PR_OK(ctx, hipSetDevice(ctx->device));
+    const size_t src_bytes = 3 * (size_t)src_w * (size_t)src_h, dst_bytes = 3 * (size_t)out_w * (size_t)out_h;
+    int st;
+    if ((st = grow(ctx, ctx->ud_src, src_bytes)) || (st = grow(ctx, ctx->ud_dst, dst_bytes))) return st;
+    apd_ud::Warp W;
+    apd_ud::fill_warp(W, params, n_params, src_w, src_h, (const uint8_t *)ctx->ud_src.p, out_K, out_w, out_h,
+                      (uint8_t *)ctx->ud_dst.p);
+    hipStream_t s = ctx->stream;
+    PR_OK(ctx, hipEventRecord(ctx->ev0, s));
+    PR_OK(ctx, hipMemcpyAsync(ctx->ud_src.p, src, src_bytes, hipMemcpyDefault, s));
+    PR_OK(ctx, hipEventRecord(ctx->ev2, s));
+    switch (model_id) {
+        case apd_ud::SIMPLE_PINHOLE: launch_undistort<apd_ud::SIMPLE_PINHOLE>(W, s); break;
+        case apd_ud::PINHOLE: launch_undistort<apd_ud::PINHOLE>(W, s); break;
+        case apd_ud::SIMPLE_RADIAL: launch_undistort<apd_ud::SIMPLE_RADIAL>(W, s); break;
+        case apd_ud::RADIAL: launch_undistort<apd_ud::RADIAL>(W, s); break;
+        case apd_ud::OPENCV: launch_undistort<apd_ud::OPENCV>(W, s); break;
+        case apd_ud::OPENCV_FISHEYE: launch_undistort<apd_ud::OPENCV_FISHEYE>(W, s); break;
+        case apd_ud::FULL_OPENCV: launch_undistort<apd_ud::FULL_OPENCV>(W, s); break;
+        case apd_ud::SIMPLE_RADIAL_FISHEYE: launch_undistort<apd_ud::SIMPLE_RADIAL_FISHEYE>(W, s); break;
+        case apd_ud::RADIAL_FISHEYE: launch_undistort<apd_ud::RADIAL_FISHEYE>(W, s); break;
+        default: launch_undistort<apd_ud::THIN_PRISM_FISHEYE>(W, s); break;
+    }
+    PR_OK(ctx, hipGetLastError());
+    PR_OK(ctx, hipEventRecord(ctx->ev3, s));
+    PR_OK(ctx, hipMemcpyAsync(dst, ctx->ud_dst.p, dst_bytes, hipMemcpyDefault, s));
+    PR_OK(ctx, hipEventRecord(ctx->ev1, s));
+    PR_OK(ctx, hipStreamSynchronize(s));
+    float up = 0.0f, ke = 0.0f, down = 0.0f;
+    PR_OK(ctx, hipEventElapsedTime(&up, ctx->ev0, ctx->ev2));
+    PR_OK(ctx, hipEventElapsedTime(&ke, ctx->ev2, ctx->ev3));
+    PR_OK(ctx, hipEventElapsedTime(&down, ctx->ev3, ctx->ev1));
+    ctx->ud_upload_ms = (double)up;
+    ctx->ud_kernel_ms = (double)ke;
+    ctx->ud_download_ms = (double)down;
+    return APD_OK;
+}
+
+int32_t apd_prep_get_undistort_timing(apd_prep_ctx *ctx, double *upload_ms, double *kernel_ms, double *download_ms) {
+    if (!ctx) return APD_EINVAL;
+    if (upload_ms) *upload_ms = ctx->ud_upload_ms;
+    if (kernel_ms) *kernel_ms = ctx->ud_kernel_ms;
+    if (download_ms) *download_ms = ctx->ud_download_ms;
     return APD_OK;
 }
 

@@ -119,11 +119,15 @@ float apdhost_view_cut_deg(float d) { return view_cut_deg(d); }
 // read_colmap_model + colmap_prep_arrays; a canonical dump (hex floats, one record per line, images in
 // ascending id) goes to dump_path if it is not NULL. Returns the number of observations or -1 with the
 // message in err.
-long apdhost_colmap_dump(const char *dir, const char *ext, const char *dump_path, char *err, long err_cap) {
+static long colmap_dump(const char *dir, const char *ext, const char *dump_path, char *err, long err_cap,
+                        bool distorted_ok) {
     ColmapModel m;
     PrepArrays a;
     std::string e;
-    if (!read_colmap_model(dir, ext, m, e) || !colmap_prep_arrays(m, a, e)) { put_err(e, err, err_cap); return -1; }
+    if (!read_colmap_model(dir, ext, m, e, distorted_ok) || !colmap_prep_arrays(m, a, e)) {
+        put_err(e, err, err_cap);
+        return -1;
+    }
     if (dump_path) {
         FILE *f = fopen(dump_path, "w");
         if (!f) { put_err("cannot write the dump", err, err_cap); return -1; }
@@ -150,6 +154,13 @@ long apdhost_colmap_dump(const char *dir, const char *ext, const char *dump_path
         if (fclose(f) != 0) { put_err("cannot write the dump", err, err_cap); return -1; }
     }
     return (long)a.obs_point.size();
+}
+long apdhost_colmap_dump(const char *dir, const char *ext, const char *dump_path, char *err, long err_cap) {
+    return colmap_dump(dir, ext, dump_path, err, err_cap, false);
+}
+// the same with the distorted camera models read too (apd_prepare --undistort; tests/test_undistort_host.py)
+long apdhost_colmap_dump_distorted(const char *dir, const char *ext, const char *dump_path, char *err, long err_cap) {
+    return colmap_dump(dir, ext, dump_path, err, err_cap, true);
 }
 int apdhost_write_cam_txt(const char *path, const double *R, const double *t, const double *K, double depth_min,
                           double interval, double depth_num, double depth_max) {

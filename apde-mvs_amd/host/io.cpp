@@ -546,13 +546,19 @@ struct Cursor {
     }
 };
 
-int model_params(const std::string &model) { return model == "SIMPLE_PINHOLE" ? 3 : model == "PINHOLE" ? 4 : 0; }
-
 const char *const kColmapModels[] = {"SIMPLE_PINHOLE", "PINHOLE", "SIMPLE_RADIAL", "RADIAL", "OPENCV", "OPENCV_FISHEYE",
                                      "FULL_OPENCV", "FOV", "SIMPLE_RADIAL_FISHEYE", "RADIAL_FISHEYE",
                                      "THIN_PRISM_FISHEYE"};
+const int kColmapModelParams[] = {3, 4, 4, 5, 8, 8, 12, 0, 4, 5, 12};  // 0: FOV, never read
 
-bool read_cameras(const std::string &path, bool bin, std::vector<ColmapCamera> &cams, std::string &err) {
+// the parameter count of a model that may be read, else 0
+int model_params(const std::string &model, bool distorted_ok) {
+    const int id = colmap_model_id(model);
+    return id < 0 || (id > 1 && !distorted_ok) ? 0 : kColmapModelParams[id];
+}
+
+bool read_cameras(const std::string &path, bool bin, bool distorted_ok, std::vector<ColmapCamera> &cams,
+                  std::string &err) {
     std::vector<uint8_t> data;
     if (!slurp(path, data, err)) return false;
     auto fail = [&](const std::string &w) { err = path + ": " + w; return false; };
@@ -565,12 +571,12 @@ bool read_cameras(const std::string &path, bool bin, std::vector<ColmapCamera> &
             ColmapCamera cam;
             int32_t model = 0;
             if (!c.get(cam.id) || !c.get(model) || !c.get(cam.width) || !c.get(cam.height)) return fail("truncated camera");
-            if (model != 0 && model != 1)
+            if (model < 0 || model > 10 || !model_params(kColmapModels[model], distorted_ok))
                 return fail("unsupported camera model " +
                             (model >= 2 && model <= 10 ? std::string(kColmapModels[model]) : "id " + std::to_string(model)) +
                             " (only SIMPLE_PINHOLE and PINHOLE; undistort the images first)");
             cam.model = kColmapModels[model];
-            cam.params.resize((size_t)model_params(cam.model));
+            cam.params.resize((size_t)model_params(cam.model, distorted_ok));
             for (double &p : cam.params)
                 if (!c.get(p) || !std::isfinite(p)) return fail("truncated or non-finite camera parameters");
             cams.push_back(cam);
@@ -588,7 +594,7 @@ bool read_cameras(const std::string &path, bool bin, std::vector<ColmapCamera> &
             cam.model = t[1];
             cam.width = (uint64_t)w;
             cam.height = (uint64_t)h;
-            const int np = model_params(cam.model);
+            const int np = model_params(cam.model, distorted_ok);
             if (!np)
                 return fail("unsupported camera model " + cam.model.substr(0, 40) +
                             " (only SIMPLE_PINHOLE and PINHOLE; undistort the images first)");
@@ -724,11 +730,18 @@ bool read_points(const std::string &path, bool bin, std::vector<int64_t> &ids, s
 }
 }  // namespace
 
-bool read_colmap_model(const std::string &dir, const std::string &ext, ColmapModel &m, std::string &err) {
+int colmap_model_id(const std::string &model) {
+    for (int id = 0; id <= 10; ++id)
+        if (id != 7 && model == kColmapModels[id]) return id;
+    return -1;
+}
+
+bool read_colmap_model(const std::string &dir, const std::string &ext, ColmapModel &m, std::string &err,
+                       bool distorted_ok) {
     m = ColmapModel();
     if (ext != ".txt" && ext != ".bin") { err = "model extension must be .txt or .bin, not '" + ext + "'"; return false; }
     const bool bin = ext == ".bin";
-    if (!read_cameras(dir + "/cameras" + ext, bin, m.cameras, err) ||
+    if (!read_cameras(dir + "/cameras" + ext, bin, distorted_ok, m.cameras, err) ||
         !read_images(dir + "/images" + ext, bin, m.images, err) ||
         !read_points(dir + "/points3D" + ext, bin, m.point_ids, m.xyz, err))
         return false;
@@ -911,10 +924,11 @@ bool scan_image_sizes(const std::string &image_dir, const std::vector<std::strin
 bool convert_scan_images(const std::string &image_dir, const std::vector<std::string> &names,
                          const std::vector<int> &widths, const std::vector<int> &heights, double scale,
                          const std::string &out_dir, std::vector<std::string> &out_names, int &out_w, int &out_h,
-                         int &copied, std::string &err) {
+                         int &copied, std::string &err, const ScanImageWarp *warp) {
     out_names.clear();
     copied = 0;
-    if (names.empty() || widths.size() != names.size() || heights.size() != names.size() || !(scale > 0)) {
+    if (names.empty() || widths.size() != names.size() || heights.size() != names.size() || !(scale > 0) ||
+        (warp && warp->mask.size() != names.size())) {
         err = "convert_scan_images: bad arguments";
         return false;
     }
@@ -929,7 +943,8 @@ bool convert_scan_images(const std::string &image_dir, const std::vector<std::st
         const size_t dot = names[i].rfind('.'), slash = names[i].rfind('/');
         if (dot != std::string::npos && (slash == std::string::npos || dot > slash)) e = names[i].substr(dot);
         for (char &c : e) c = (char)tolower((unsigned char)c);
-        const bool as_is = scale == 1.0 && widths[i] == max_w && heights[i] == max_h &&
+        const bool warped = warp && warp->mask[i];
+        const bool as_is = !warped && scale == 1.0 && widths[i] == max_w && heights[i] == max_h &&
                            (e == ".jpg" || e == ".jpeg" || e == ".png");
         const std::string name = format_index((int)i) + (as_is ? e : ".png");
         for (const char *stale : {".jpg", ".jpeg", ".png"})
@@ -941,6 +956,14 @@ bool convert_scan_images(const std::string &image_dir, const std::vector<std::st
             Bgr8 img;
             if (!read_bgr8(src, img, err)) return false;
             if (img.width != widths[i] || img.height != heights[i]) { err = src + " changed size"; return false; }
+            if (warped) {
+                if (!warp->apply(i, img, err)) return false;
+                if (img.width != widths[i] || img.height != heights[i] ||
+                    img.px.size() != 3 * (size_t)img.width * (size_t)img.height) {
+                    err = "the warp of " + src + " changed its size";
+                    return false;
+                }
+            }
             std::vector<uint8_t> pad(3 * (size_t)max_w * max_h, 0);
             for (int r = 0; r < img.height; ++r)
                 memcpy(&pad[3 * (size_t)r * max_w], &img.px[3 * (size_t)r * img.width], 3 * (size_t)img.width);

@@ -4,6 +4,7 @@
 #pragma once
 
 #include <cstdint>
+#include <functional>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -126,9 +127,9 @@ void mlp_to_world(const MlpMesh &m, std::vector<float> &xyz, float origin[3]);
 // ---- COLMAP sparse models (apd_prepare; the reference's tools/colmap2mvsnet.py) ---------------------
 struct ColmapCamera {
     uint32_t id = 0;
-    std::string model;  // SIMPLE_PINHOLE or PINHOLE
+    std::string model;  // SIMPLE_PINHOLE or PINHOLE; with distorted_ok any of include/apd_prep.h's models
     uint64_t width = 0, height = 0;
-    std::vector<double> params;  // f cx cy | fx fy cx cy
+    std::vector<double> params;  // the model's own count and order: f cx cy | fx fy cx cy | f cx cy k | ...
 };
 struct ColmapImage {
     uint32_t id = 0, camera_id = 0;
@@ -147,7 +148,12 @@ struct ColmapModel {
 // PINHOLE cameras are accepted, as in the reference. Every count is bounded by the file's size before
 // anything is allocated; truncated or garbled files, non-numeric tokens, non-finite numbers, duplicate
 // ids and an image whose camera is missing are rejected with a message in `err`.
-bool read_colmap_model(const std::string &dir, const std::string &ext, ColmapModel &m, std::string &err);
+// With distorted_ok (apd_prepare --undistort) the eight distorted models of include/apd_prep.h are
+// read too, each with its own parameter count; FOV and unknown models are rejected either way.
+bool read_colmap_model(const std::string &dir, const std::string &ext, ColmapModel &m, std::string &err,
+                       bool distorted_ok = false);
+// COLMAP's id of a model name that include/apd_prep.h supports (0..6, 8..10), else -1
+int colmap_model_id(const std::string &model);
 
 // The arrays of apd_prep_set_model (include/apd_prep.h): R by the contract's qvec formula, centres,
 // and the observations as indices into the point array, grouped by image. A point id an image names
@@ -183,12 +189,20 @@ bool copy_file(const std::string &from, const std::string &to);
 // (int(W/scale), int(H/scale)) by resize_nearest and written as 8-bit colour PNG (there is no JPEG
 // encoder here: lossless, where the reference recompresses). Files %08d.{jpg,jpeg,png} of another
 // extension left by an earlier run are removed, so every index has one image.
+// With `warp`, an image i with warp->mask[i] is never copied: it is decoded, handed to warp->apply
+// (which replaces its pixels and keeps its size; false with a message in `err` fails the call) and
+// then padded, resized and written as PNG like any other decoded image.
+struct Bgr8;  // image.h
+struct ScanImageWarp {
+    std::vector<char> mask;  // one entry per image
+    std::function<bool(size_t, Bgr8 &, std::string &)> apply;
+};
 bool scan_image_sizes(const std::string &image_dir, const std::vector<std::string> &names, std::vector<int> &widths,
                       std::vector<int> &heights, std::string &err);
 bool convert_scan_images(const std::string &image_dir, const std::vector<std::string> &names,
                          const std::vector<int> &widths, const std::vector<int> &heights, double scale,
                          const std::string &out_dir, std::vector<std::string> &out_names, int &out_w, int &out_h,
-                         int &copied, std::string &err);
+                         int &copied, std::string &err, const ScanImageWarp *warp = nullptr);
 
 std::string format_index(int id);  // ToFormatIndex: %08d
 bool file_exists(const std::string &p);

@@ -3,6 +3,9 @@
 // The reference's tools/colmap2mvsnet.py without cv2/tqdm; covisibility pair counts and per-image depth
 // ranks on the device (include/apd_prep.h). Every input is read and validated before a device context
 // exists (exit 2); device or write failures exit 1.
+// With --undistort the images of cameras with a distorted model are warped on the device into pinhole
+// images of the same size and fx fy cx cy (include/apd_prep.h, "Undistortion"), their cameras are
+// written as PINHOLE and their keypoints are carried along; pinhole cameras go the usual way.
 #include <algorithm>
 #include <cctype>
 #include <cmath>
@@ -25,7 +28,7 @@ namespace {
 const char *kUsage =
     "usage: apd_prepare --dense_folder IN --save_folder OUT [options]\n"
     "  A COLMAP sparse model and its undistorted (PINHOLE) images -> OUT/cams, OUT/images, OUT/pair.txt,\n"
-    "  OUT/sparse/0: the scan layout `apd` reads.\n"
+    "  OUT/sparse/0: the scan layout `apd` reads. Distorted images: see --undistort.\n"
     "  --dense_folder IN        holds sparse/ and images/ unless the next two say otherwise\n"
     "  --model_dir DIR          cameras/images/points3D (default IN/sparse)\n"
     "  --image_dir DIR          the images; names may carry a sub-directory (default IN/images)\n"
@@ -39,6 +42,12 @@ const char *kUsage =
     "  --theta0 --sigma1 --sigma2      accepted and unused, as in the reference\n"
     "  --device G               HIP device (default 0)\n"
     "  --json OUT.json          counts and device times\n"
+    "  --undistort              also accept SIMPLE_RADIAL, RADIAL, OPENCV, OPENCV_FISHEYE, FULL_OPENCV,\n"
+    "                           SIMPLE_RADIAL_FISHEYE, RADIAL_FISHEYE and THIN_PRISM_FISHEYE cameras (not FOV):\n"
+    "                           their images are warped on the device to pinhole images of the same size and\n"
+    "                           fx fy cx cy (bilinear, black where there is no source) and written as PNG, their\n"
+    "                           cameras become PINHOLE and their keypoints in sparse/0/images.txt are undistorted\n"
+    "                           ((-1, -1) where that fails). Without it such models are rejected.\n"
     "  Images are copied byte for byte when they are JPEG/PNG, need no padding and F = 1; otherwise they are\n"
     "  padded bottom/right to the largest size, resized (nearest) and written as 8-bit colour PNG.\n";
 
@@ -46,7 +55,7 @@ struct Options {
     std::string dense, save, model_dir, image_dir, ext = ".txt", json;
     int max_d = 192, seq_k = 5, max_views = 20, device = 0;
     double interval_scale = 1.0, scale = 1.0;
-    bool sequential = true;
+    bool sequential = true, undistort = false;
 };
 
 bool parse_double(const std::string &s, double &v) {
@@ -84,6 +93,7 @@ int main(int argc, char **argv) {
         if (a == "--help" || a == "-h") { std::cout << kUsage; return 0; }
         if (a == "--sequential") { seq_set = true; continue; }
         if (a == "--no-sequential") { noseq_set = true; continue; }
+        if (a == "--undistort") { opt.undistort = true; continue; }
         if (i + 1 >= argc) return usage_error("missing value for " + a);
         const std::string v = argv[++i];
         double unused;
@@ -118,8 +128,11 @@ int main(int argc, char **argv) {
     ColmapModel model;
     PrepArrays arr;
     std::string err;
-    if (!read_colmap_model(opt.model_dir, opt.ext, model, err) || !colmap_prep_arrays(model, arr, err)) {
+    if (!read_colmap_model(opt.model_dir, opt.ext, model, err, opt.undistort) || !colmap_prep_arrays(model, arr, err)) {
         std::cerr << "apd_prepare: " << err << "\n";
+        if (!opt.undistort && err.find("unsupported camera model") != std::string::npos &&
+            err.find("unsupported camera model FOV") == std::string::npos)
+            std::cerr << "apd_prepare: (or pass --undistort, if it is one of the models --help lists)\n";
         return 2;
     }
     const int n = (int)model.images.size();
@@ -141,6 +154,33 @@ int main(int argc, char **argv) {
             std::cerr << "apd_prepare: --scale_factor leaves no pixels\n";
             return 2;
         }
+    }
+
+    // distorted cameras (only with --undistort): the library's own argument rules, and an image of
+    // the size its camera states, since that is the size its parameters are for
+    auto source_camera = [&](uint32_t id) -> const ColmapCamera & {
+        for (const ColmapCamera &c : model.cameras)
+            if (c.id == id) return c;
+        return model.cameras[0];  // read_colmap_model has checked that every image's camera exists
+    };
+    std::vector<char> distorted((size_t)n, 0);
+    int n_distorted = 0;
+    for (int i = 0; i < n; ++i) {
+        const ColmapCamera &c = source_camera(model.images[(size_t)i].camera_id);
+        const int id = colmap_model_id(c.model);
+        if (id <= 1) continue;
+        const bool one_f = c.params.size() == 4 || c.params.size() == 5;
+        if (!(c.params[0] > 0) || (!one_f && !(c.params[1] > 0))) {
+            std::cerr << "apd_prepare: camera " << c.id << ": a focal length that is not positive\n";
+            return 2;
+        }
+        if ((uint64_t)widths[(size_t)i] != c.width || (uint64_t)heights[(size_t)i] != c.height) {
+            std::cerr << "apd_prepare: " << names[(size_t)i] << " is " << widths[(size_t)i] << "x" << heights[(size_t)i]
+                      << ", its " << c.model << " camera " << c.id << " says " << c.width << "x" << c.height << "\n";
+            return 2;
+        }
+        distorted[(size_t)i] = 1;
+        ++n_distorted;
     }
 
     // ---- device: depth ranks, and pair counts unless sequential ----
@@ -176,19 +216,30 @@ int main(int argc, char **argv) {
     }
     double tracks_ms = 0, pairs_ms = 0, records_ms = 0, ranks_ms = 0;
     apd_prep_get_timing(ctx, &tracks_ms, &pairs_ms, &records_ms, &ranks_ms);
-    apd_prep_destroy(ctx);
+    if (n_distorted == 0) {  // else the context lives until the images are warped
+        apd_prep_destroy(ctx);
+        ctx = nullptr;
+    }
 
     // ---- write ----
     auto write_fail = [&](const std::string &what) {
         std::cerr << "apd_prepare: cannot write " << what << "\n";
+        if (ctx) apd_prep_destroy(ctx);
         return 1;
     };
     if (!make_dir(opt.save) || !make_dir(opt.save + "/cams") || !make_dir(opt.save + "/images") ||
         !make_dir(opt.save + "/sparse") || !make_dir(opt.save + "/sparse/0"))
         return write_fail(opt.save);
     std::vector<ColmapCamera> cams = model.cameras;
-    for (ColmapCamera &c : cams)
+    for (ColmapCamera &c : cams) {
+        if (colmap_model_id(c.model) > 1) {  // the warped images' camera: PINHOLE fx fy cx cy
+            const bool one_f = c.params.size() == 4 || c.params.size() == 5;
+            const std::vector<double> p = c.params;
+            c.params = one_f ? std::vector<double>{p[0], p[0], p[1], p[2]} : std::vector<double>{p[0], p[1], p[2], p[3]};
+            c.model = "PINHOLE";
+        }
         for (double &p : c.params) p = p / opt.scale;
+    }
     auto camera_of = [&](uint32_t id) -> ColmapCamera & {
         for (ColmapCamera &c : cams)
             if (c.id == id) return c;
@@ -216,14 +267,53 @@ int main(int argc, char **argv) {
 
     int copied = 0, out_w = 0, out_h = 0;
     std::vector<std::string> out_names;
-    if (!convert_scan_images(opt.image_dir, names, widths, heights, opt.scale, opt.save + "/images", out_names, out_w,
-                             out_h, copied, err)) {
+    double ud_upload_ms = 0, ud_kernel_ms = 0, ud_download_ms = 0;
+    ScanImageWarp warp;
+    warp.mask = distorted;
+    warp.apply = [&](size_t i, Bgr8 &img, std::string &e) {
+        const ColmapCamera &c = source_camera(model.images[i].camera_id);
+        const bool one_f = c.params.size() == 4 || c.params.size() == 5;
+        const double K[4] = {c.params[0], one_f ? c.params[0] : c.params[1], c.params[one_f ? 1 : 2],
+                             c.params[one_f ? 2 : 3]};
+        std::vector<uint8_t> out(img.px.size());
+        if (apd_prep_undistort_bgr8(ctx, colmap_model_id(c.model), c.params.data(), (int32_t)c.params.size(), img.width,
+                                    img.height, img.px.data(), K, img.width, img.height, out.data()) != APD_OK) {
+            e = std::string("apd_prep_undistort_bgr8: ") + apd_prep_last_error(ctx);
+            return false;
+        }
+        double up = 0, ke = 0, down = 0;
+        apd_prep_get_undistort_timing(ctx, &up, &ke, &down);
+        ud_upload_ms += up;
+        ud_kernel_ms += ke;
+        ud_download_ms += down;
+        img.px.swap(out);
+        return true;
+    };
+    const bool converted_ok = convert_scan_images(opt.image_dir, names, widths, heights, opt.scale, opt.save + "/images",
+                                                  out_names, out_w, out_h, copied, err, n_distorted ? &warp : nullptr);
+    if (ctx) {
+        apd_prep_destroy(ctx);
+        ctx = nullptr;
+    }
+    if (!converted_ok) {
         std::cerr << "apd_prepare: " << err << "\n";
         return 1;
     }
     const int converted = n - copied;
     std::vector<ColmapImage> out_images = model.images;
+    int64_t unresolved = 0;
     for (int i = 0; i < n; ++i) {
+        if (distorted[(size_t)i]) {  // the list keeps its length and order: points3D refers to it by index
+            const ColmapCamera &c = source_camera(model.images[(size_t)i].camera_id);
+            std::vector<double> &xy = out_images[(size_t)i].xy;
+            int64_t bad = 0;
+            if (apd_prep_undistort_xy(colmap_model_id(c.model), c.params.data(), (int32_t)c.params.size(),
+                                      (int64_t)(xy.size() / 2), xy.data(), xy.data(), &bad) != APD_OK) {
+                std::cerr << "apd_prepare: apd_prep_undistort_xy failed for image " << model.images[(size_t)i].id << "\n";
+                return 1;
+            }
+            unresolved += bad;
+        }
         out_images[(size_t)i].name = out_names[(size_t)i];
         ColmapCamera &c = camera_of(model.images[(size_t)i].camera_id);
         c.width = (uint64_t)out_w;
@@ -240,7 +330,13 @@ int main(int argc, char **argv) {
                        ", \"width\": " + std::to_string(out_w) + ", \"height\": " + std::to_string(out_h) +
                        ", \"images_copied\": " + std::to_string(copied) + ", \"images_converted\": " +
                        std::to_string(converted) + ", \"tracks_ms\": " + fmt_g(tracks_ms) + ", \"pairs_ms\": " +
-                       fmt_g(pairs_ms) + ", \"records_ms\": " + fmt_g(records_ms) + ", \"ranks_ms\": " + fmt_g(ranks_ms) + "}";
+                       fmt_g(pairs_ms) + ", \"records_ms\": " + fmt_g(records_ms) + ", \"ranks_ms\": " + fmt_g(ranks_ms);
+    if (opt.undistort)
+        json += ", \"images_undistorted\": " + std::to_string(n_distorted) + ", \"keypoints_unresolved\": " +
+                std::to_string(unresolved) + ", \"undistort_upload_ms\": " + fmt_g(ud_upload_ms) +
+                ", \"undistort_kernel_ms\": " + fmt_g(ud_kernel_ms) + ", \"undistort_download_ms\": " +
+                fmt_g(ud_download_ms);
+    json += "}";
     std::cout << json << std::endl;
     if (!opt.json.empty()) {
         std::ofstream o(opt.json);
