@@ -292,10 +292,20 @@ __device__ __forceinline__ void tile_coords(int t, int tiles_x, int tiles_y, int
     tx = SX * sx + r2 % cols;
     ty = SY * sy + r2 / cols;
 }
-__device__ __forceinline__ void tile_pixel(int tile, int tiles_x, int tiles_y, int tw, int k, int &x, int &y) {
+// quad: the micro-tiles in 2x2 blocks (blocks row-major inside the tile, micro-tiles row-major inside a
+// block), so that 64 consecutive positions are an 8x8 block instead of a 16x4 strip (the dense WEAK
+// list, whose 64-entry groups hold both colours). Needs a tile of at least 8x8 (tile_quad_ok).
+__host__ __device__ __forceinline__ bool tile_quad_ok(int tw) { return tw >= 8 && TILE_POS / tw >= 8; }
+__device__ __forceinline__ void tile_pixel(int tile, int tiles_x, int tiles_y, int tw, int k, int &x, int &y, bool quad = false) {
     const int micro = k >> 4, inner = k & 15, mx = tw >> 2;
-    const int lx = ((micro % mx) << 2) + (inner & 3);
-    const int ly = ((micro / mx) << 2) + (inner >> 2);
+    int mcol = micro % mx, mrow = micro / mx;
+    if (quad) {
+        const int q = micro >> 2, i = micro & 3, qx = mx >> 1;
+        mcol = ((q % qx) << 1) + (i & 1);
+        mrow = ((q / qx) << 1) + (i >> 1);
+    }
+    const int lx = (mcol << 2) + (inner & 3);
+    const int ly = (mrow << 2) + (inner >> 2);
     int tx, ty;
     tile_coords(tile, tiles_x, tiles_y, tw, tx, ty);
     x = tx * tw + lx;
@@ -313,9 +323,9 @@ __global__ __launch_bounds__(BLOCK) void k_tile_count(Args a, int mode, int colo
     if (threadIdx.x == 0) counts[blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
 }
 __global__ __launch_bounds__(BLOCK) void k_tile_fill(Args a, int mode, int colour, int tiles_x, int tw,
-                                                   const int *__restrict__ offs, int *__restrict__ out) {
+                                                   const int *__restrict__ offs, int *__restrict__ out, int quad) {
     int x, y;
-    tile_pixel(blockIdx.x, tiles_x, (int)gridDim.x / tiles_x, tw, threadIdx.x, x, y);
+    tile_pixel(blockIdx.x, tiles_x, (int)gridDim.x / tiles_x, tw, threadIdx.x, x, y, quad != 0);
     const bool p = x < a.W && y < a.H && list_pred(a, mode, colour, x, y);
     __shared__ int wcnt[BLOCK / WAVE];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -2198,6 +2208,15 @@ __device__ __forceinline__ float ncc_new_vm(const Args &a, const WvRefT<F16, NWI
 #define WV_P2_GEOM_BATCH 0
 #endif
 #define WV_BLOCK (WV_WAVES * WAVE)
+// The anchor candidates' costs (k_weak_cand_g writes, k_weak_cand_comb combines in place, the Weak
+// sweep's P2a reads). gm: [group][view][candidate][VM_P] by the position li in the dense WEAK list, the
+// same 64-entry groups in all three kernels, so a group's N * 8 segments are one contiguous block; else
+// [view][candidate][WEAK index wi] (segments wc * 4 B apart; the per-colour sweep, whose groups are not
+// the candidate kernels').
+__device__ __forceinline__ size_t cand_at(bool gm, int N, int v, int h, int wc, int wi, int li) {
+    return gm ? ((size_t)(li / VM_P) * (size_t)(N * 8) + (size_t)(v * 8 + h)) * VM_P + (size_t)(li % VM_P)
+              : ((size_t)v * 8 + h) * (size_t)wc + (size_t)wi;
+}
 template <bool F16, bool SA> struct WvOcc {
 #ifdef WV_LDS_OCC
     static constexpr int occ = WV_LDS_OCC;
@@ -2208,7 +2227,7 @@ template <bool F16, bool SA> struct WvOcc {
 };
 template <bool F16, bool SA>
 __global__ __launch_bounds__(WV_BLOCK, (WvOcc<F16, SA>::occ)) void k_sweep_weak_vm(Args a, const int *__restrict__ list, int count,
-                                                                int iter, const float *__restrict__ cand, int wc) {
+                                                                int iter, const float *__restrict__ cand, int wc, int gm) {
     const int N = a.N, W = a.W;
     constexpr bool PIPE = WvOcc<F16, SA>::pipe;
     PHASE_BEGIN;
@@ -2368,10 +2387,11 @@ __global__ __launch_bounds__(WV_BLOCK, (WvOcc<F16, SA>::occ)) void k_sweep_weak_
         }
         float ca[8];
         if (direct) {  // the candidates' costs from the pair-table kernels; absent ones as P1 sets them
-            const size_t wi = (size_t)a.amap[c];
+            const float *cp = cand + cand_at(gm != 0, N, v, 0, wc, gm ? 0 : a.amap[c], first + p);
+            const size_t hs = gm ? (size_t)VM_P : (size_t)wc;  // candidate stride
 #pragma unroll
             for (int h = 0; h < 8; ++h)
-                ca[h] = ((hflag >> h) & 1u) ? cand[((size_t)v * 8 + h) * (size_t)wc + wi] : ((h == 0 && v == 0) ? 2.0f : 0.0f);
+                ca[h] = ((hflag >> h) & 1u) ? cp[h * hs] : ((h == 0 && v == 0) ? 2.0f : 0.0f);
         } else {
 #pragma unroll
             for (int h = 0; h < 8; ++h) ca[h] = costL[(h * N + v) * VM_P + p];
@@ -2810,7 +2830,7 @@ __global__ __launch_bounds__(WV_BLOCK, (WvOcc<F16, SA>::occ)) void k_sweep_weak_
 //   per iteration: k_gp_cost evaluates every pair in every view (lane = pair, consecutive pairs share
 //     a window anchor) into pcost[pair][view]; k_weak_cand_g evaluates the centre windows (lane =
 //     pixel, wave = candidate) and the focal combination reading the pair costs, and writes the same
-//     [view][candidate][WEAK index] costs the sweep reads (direct mode).
+//     costs the sweep reads (direct mode; layout: cand_at).
 // ---------------------------------------------------------------------------------------------
 #ifndef GP_CHUNK
 #define GP_CHUNK 256   // references per batch of k_gp_dedup (one workgroup per window anchor)
@@ -3386,13 +3406,13 @@ __device__ __forceinline__ float gp_combine(float cc, const float (&sc)[8]) {
 
 // the anchor candidates' centre windows (k_weak_cand_comb then combines them with the pair costs);
 // lane = pixel, wave = candidate h. Per view (the waves take the views together: one source image,
-// the CU's L1) the centre window of (pixel, h) -> out[v][h][WEAK index] (-1: dead, the pixel or its
+// the CU's L1) the centre window of (pixel, h) -> out at cand_at (-1: dead, the pixel or its
 // anchor 0 projected out of frame). With an SA label at the pixel the centre window is used only
 // when anchor 0 carries the label (else center_cost stays 0, APD.cu:493-497) and its taps are
 // filtered by it (APD.cu:526-530); an empty window leaves center_cost 0 (APD.cu:543).
 template <bool F16, bool SA>
 __global__ __launch_bounds__(PK_BLOCK, PK_MINW) void k_weak_cand_g(Args a, const int *__restrict__ list, int count,
-                                                          const uint8_t *__restrict__ cbw, float *__restrict__ out, int wc) {
+                                                          const uint8_t *__restrict__ cbw, float *__restrict__ out, int wc, int gm) {
     using TT = FastTex<F16, true>;  // (FastTexD measured 1.4 % slower per iteration here, profiles/r5_ab_dtex_kernels.txt)
     // (fp16 reference taps when the images are: fp32 measured 6 % slower, profiles/r4_ab_cand_g_fp32_ref.txt)
     using RT = typename std::conditional<F16, _Float16, float>::type;
@@ -3498,7 +3518,7 @@ __global__ __launch_bounds__(PK_BLOCK, PK_MINW) void k_weak_cand_g(Args a, const
         }
         nlive += live;
         // (k_weak_cand_comb reads it back and writes the candidate's cost in its place)
-        if (want) out[((size_t)v * 8 + h) * (size_t)wc + wi1] = dead ? -1.0f : center_cost;
+        if (want) out[cand_at(gm != 0, N, v, h, wc, wi1, first + p1)] = dead ? -1.0f : center_cost;
     }
     if (a.evals) wave_count(a.evals, 6, nlive);  // (profiling: centre windows evaluated)
 }
@@ -3514,7 +3534,7 @@ __global__ __launch_bounds__(PK_BLOCK, PK_MINW) void k_weak_cand_g(Args a, const
 __global__ __launch_bounds__(BLOCK) void k_weak_cand_comb(Args a, const int *__restrict__ list, int count,
                                                           const uint8_t *__restrict__ cbw, const uint8_t *__restrict__ wmw,
                                                           const uint32_t *__restrict__ pidx,
-                                                          const float *__restrict__ pcost, float *__restrict__ out, int wc) {
+                                                          const float *__restrict__ pcost, float *__restrict__ out, int wc, int gm) {
     __shared__ uint32_t sid[VM_P * COMB_STRIDE];
     const int b = xcd_remap(blockIdx.x, gridDim.x);
     const int h0 = (b & 1) << 2, hl = threadIdx.x >> 6, h = h0 + hl;
@@ -3553,7 +3573,7 @@ __global__ __launch_bounds__(BLOCK) void k_weak_cand_comb(Args a, const int *__r
             float sc[8];
 #pragma unroll
             for (int k = 0; k < 8; ++k) sc[k] = dv == 0 ? q[k].x : dv == 1 ? q[k].y : dv == 2 ? q[k].z : q[k].w;
-            float *o = out + ((size_t)v * 8 + h) * (size_t)wc + wi;
+            float *o = out + cand_at(gm != 0, N, v, h, wc, wi, i);
             *o = gp_combine(*o, sc);
         }
     }
@@ -4382,6 +4402,11 @@ struct apd_ctx {
                                    // (16 x 16: -1 % per C3 iteration against 8 x 32, profiles/r4_ab_tile_shape.txt)
     bool cand_pairs = true;        // Weak sweep candidates through the image-wide pair table; APD_NO_CAND_PAIRS=1
                                    // leaves them to the sweep
+    bool weak_per_colour = false;  // APD_WEAK_PER_COLOUR=1: the Weak sweep once per colour over per-colour lists (A/B, parity)
+    bool weak_quad = false;        // APD_WEAK_QUAD=1: the WEAK index and the dense WEAK list in 8x8 blocks instead of 16x4
+                                   // strips (no fewer distinct anchors per group: profiles/weak_group_sharing.txt)
+    bool cand_gm = true;           // the candidates' costs as [group][view][candidate][64]; APD_NO_CAND_GROUP_MAJOR=1 (and
+                                   // the per-colour sweep): [view][candidate][WEAK index]
     bool gp_on = false;            // the pair table of the prepared problem is built (apd_stage_prepare)
     bool ga_split = true;          // GenAnchors' RANSAC in k_gen_anchors_fit; APD_NO_GA_SPLIT=1: in k_gen_anchors
     bool rec_on = false;           // the anchor-window records of the prepared problem are built (k_anchor_rec)
@@ -4632,6 +4657,9 @@ apd_ctx *apd_create(int32_t device) {
     for (auto &e : ctx->ev_side) (void)hipEventCreateWithFlags(&e, hipEventDisableTiming);
     ctx->overlap = getenv("APD_NO_OVERLAP") == nullptr;
     ctx->cand_pairs = getenv("APD_NO_CAND_PAIRS") == nullptr;
+    ctx->weak_per_colour = getenv("APD_WEAK_PER_COLOUR") != nullptr;
+    ctx->weak_quad = getenv("APD_WEAK_QUAD") != nullptr;
+    ctx->cand_gm = getenv("APD_NO_CAND_GROUP_MAJOR") == nullptr && !ctx->weak_per_colour;
     ctx->ga_split = getenv("APD_NO_GA_SPLIT") == nullptr;
     ctx->lr_handover = getenv("APD_NO_LR_HANDOVER") == nullptr;
     ctx->wcur_on = getenv("APD_NO_WCUR") == nullptr;
@@ -4958,13 +4986,14 @@ static void tile_count_scan(apd_ctx *ctx, int mode, int colour, int *total_dev) 
     hipLaunchKernelGGL(k_list_scan, dim3(1), dim3(1024), 0, ctx->stream, (const int *)ctx->rowcnt.p, tx * ty,
                        (int *)ctx->rowoff.p, total_dev);
 }
-static int build_tile_list(apd_ctx *ctx, int mode, int colour, int *out, int *total_dev) {
+// (quad: tile_pixel's 8x8-block order inside the tiles -- the WEAK index and the dense WEAK list)
+static int build_tile_list(apd_ctx *ctx, int mode, int colour, int *out, int *total_dev, bool quad = false) {
     Args &a = ctx->args;
     const int tw = ctx->tile_w, th = TILE_POS / tw;
     const int tx = (a.W + tw - 1) / tw, ty = (a.H + th - 1) / th;
     tile_count_scan(ctx, mode, colour, total_dev);
     hipLaunchKernelGGL(k_tile_fill, dim3(tx * ty), dim3(BLOCK), 0, ctx->stream, a, mode, colour, tx, tw,
-                       (const int *)ctx->rowoff.p, out);
+                       (const int *)ctx->rowoff.p, out, (quad && tile_quad_ok(tw)) ? 1 : 0);
     return check_launch(ctx, "tile list build");
 }
 // anchors_map (mode 2) in row-major order (APD.cpp:627-640)
@@ -4985,6 +5014,10 @@ static int *list_ptr(apd_ctx *ctx, int which) {
     size_t off = 0;
     for (int i = 0; i < which; ++i) off += (size_t)ctx->cnt[i];
     return base + off;
+}
+// bytes of the candidates' costs in either layout of cand_at (wc WEAK pixels, nw of them listed)
+static size_t wcand_bytes(int N, size_t wc, int nw) {
+    return (size_t)N * 8 * std::max(wc, (size_t)blocks_for((size_t)nw, VM_P) * VM_P) * sizeof(float);
 }
 
 
@@ -5205,7 +5238,7 @@ int32_t apd_stage_prepare(apd_ctx *ctx) {
         // the tile-ordered kernels (row-major, a 64-pixel list chunk scattered its 4-byte writes over
         // 4 rows: k_weak_cand_comb wrote 2.2x its bytes). Only the anchors export sees the numbering,
         // and apd_result restores the row-major order.
-        if ((st = build_tile_list(ctx, 2, 0, (int *)ctx->amap.p, (int *)ctx->totals.p + 4))) return st;
+        if ((st = build_tile_list(ctx, 2, 0, (int *)ctx->amap.p, (int *)ctx->totals.p + 4, ctx->weak_quad))) return st;
         if (ctx->near_levels) {
             hipLaunchKernelGGL(k_near_columns, dim3(blocks_for((size_t)ctx->near_levels * a.W, BLOCK)), dim3(BLOCK), 0, s, a,
                                ctx->near_levels, (uint8_t *)ctx->near_g.p);
@@ -5277,18 +5310,22 @@ int32_t apd_stage_prepare(apd_ctx *ctx) {
         HIP_OK(ctx, hipMemcpyAsync(host_tot, tot, 4 * sizeof(int), hipMemcpyDeviceToHost, s));
         HIP_OK(ctx, hipStreamSynchronize(s));
         for (int i = 0; i < 4; ++i) ctx->cnt[i] = host_tot[i];
-        for (int i = 0; i < 4; ++i) {
+        // (the per-colour WEAK lists only for the per-colour Weak sweep, APD_WEAK_PER_COLOUR=1)
+        for (int i = 0; i < (ctx->weak_per_colour ? 4 : 2); ++i) {
             if ((st = build_tile_list(ctx, modes[i][0], modes[i][1], list_ptr(ctx, i), tot + i))) return st;
         }
-        if (a.use_apd && ctx->cand_pairs && ctx->cnt[2] + ctx->cnt[3] > 0) {
-            // the anchor candidates' kernels run once per iteration over the WEAK pixels of both
-            // colours (tile order): between the two Weak launches no anchor plane or selection
-            // changes. Costs are kept by WEAK index.
+        const int nw = ctx->cnt[2] + ctx->cnt[3];
+        if (a.use_apd && nw > 0) {
+            // the Weak sweep and the anchor candidates' kernels run once per iteration over the WEAK
+            // pixels of both colours (tile order, dense 64-entry groups): see apd_stage_iteration
+            if ((st = ensure(ctx, ctx->wlist, (size_t)nw * sizeof(int)))) return st;
+            if ((st = build_tile_list(ctx, 1, 2, (int *)ctx->wlist.p, tot + 5, ctx->weak_quad))) return st;
+        }
+        if (a.use_apd && ctx->cand_pairs && nw > 0) {
+            // the candidates' costs, by the dense list's groups (cand_at) or by WEAK index
             const size_t wc = (size_t)std::max(ctx->weak_count, 1);
             if (test_enomem_hook(ctx)) return APD_ENOMEM;  // (RandomInitialization is in flight on side stream 0)
-            if ((st = ensure(ctx, ctx->wcand, (size_t)a.N * 8 * wc * sizeof(float)))) return st;
-            if ((st = ensure(ctx, ctx->wlist, (size_t)(ctx->cnt[2] + ctx->cnt[3]) * sizeof(int)))) return st;
-            if ((st = build_tile_list(ctx, 1, 2, (int *)ctx->wlist.p, tot + 5))) return st;
+            if ((st = ensure(ctx, ctx->wcand, wcand_bytes(a.N, wc, nw)))) return st;
             (void)hipEventRecord(ctx->ev[14], s);
             // (the table's keys hold a pixel index below 2^25 and x below 2^15; else the sweep
             // evaluates the candidates itself)
@@ -5397,8 +5434,9 @@ int32_t apd_stage_iteration(apd_ctx *ctx, int32_t iter) {
         const int nw = ctx->cnt[2] + ctx->cnt[3];
         const int wc = std::max(ctx->weak_count, 1);
         const float *cand = nullptr;
+        const int gm = ctx->cand_gm ? 1 : 0;  // the candidates' costs by the dense list's groups (cand_at)
         if (ctx->cand_pairs && nw > 0 && ctx->gp_on) {
-            if (ctx->wcand.bytes < (size_t)a.N * 8 * (size_t)wc * sizeof(float) || ctx->wlist.bytes < (size_t)nw * sizeof(int)) {
+            if (ctx->wcand.bytes < wcand_bytes(a.N, (size_t)wc, nw) || ctx->wlist.bytes < (size_t)nw * sizeof(int)) {
                 ctx->err = "candidate cost buffers not sized by apd_stage_prepare";
                 return APD_ESTATE;
             }
@@ -5413,20 +5451,33 @@ int32_t apd_stage_iteration(apd_ctx *ctx, int32_t iter) {
                 if (ctx->overlap) HIP_OK(ctx, hipEventRecord(ctx->ev_side[1], sg));
                 e1 = prof_begin(ctx);
                 LAUNCH_TEX_SA(k_weak_cand_g, dim3(blocks_for((size_t)nw, VM_P)), dim3(PK_BLOCK), 0, s, ac, (const int *)ctx->wlist.p, nw,
-                              (const uint8_t *)ctx->gp_cb.p, (float *)ctx->wcand.p, wc);
+                              (const uint8_t *)ctx->gp_cb.p, (float *)ctx->wcand.p, wc, gm);
                 prof_end(ctx, e1, APD_PROF_WEAK_CAND_G, nw);
                 if (ctx->overlap) HIP_OK(ctx, hipStreamWaitEvent(s, ctx->ev_side[1], 0));  // join k_gp_cost
                 e1 = prof_begin(ctx);
                 hipLaunchKernelGGL(k_weak_cand_comb, dim3(2 * blocks_for((size_t)nw, VM_P)), dim3(BLOCK), 0, s, ac,
                                    (const int *)ctx->wlist.p, nw, (const uint8_t *)ctx->gp_cb.p, (const uint8_t *)ctx->gp_cb.p + wc,
-                                   (const uint32_t *)ctx->gp_pidx.p, (const float *)ctx->gp_pcost.p, (float *)ctx->wcand.p, wc);
+                                   (const uint32_t *)ctx->gp_pidx.p, (const float *)ctx->gp_pcost.p, (float *)ctx->wcand.p, wc, gm);
                 prof_end(ctx, e1, APD_PROF_WEAK_CAND_COMB, nw);
             }
             cand = (const float *)ctx->wcand.p;
         }
         if (ctx->overlap) HIP_OK(ctx, hipStreamWaitEvent(s, ctx->ev_side[0], 0));  // join RANSAC (the sweep reads a.fit)
-        for (int colour = 0; colour < 2; ++colour) {
-            const int n = ctx->cnt[2 + colour];
+        // One Weak launch over the dense two-colour list. The checkerboard buys nothing here: for a
+        // pixel other than its own the sweep reads only its anchors' state, label, plane and selection
+        // (a.weak, a.sa, a.plane, a.sel at anchors 1..8, which come from the nearest-STRONG map; anchor
+        // 0 is the pixel itself), and it writes a.plane, a.cost, a.sel and a.vw at WEAK pixels only.
+        // No anchor 1..8 is a WEAK pixel, so nothing one workgroup writes is read by another: the
+        // anchors' entries were last written by the Strong sweeps, earlier on this stream, and a.fit by
+        // the RANSAC joined above. The source views, a.depth and the candidates' costs are read-only
+        // here. APD_WEAK_PER_COLOUR=1 keeps the launch per colour over the per-colour lists.
+        if (!ctx->weak_per_colour && nw > 0 && ctx->wlist.bytes < (size_t)nw * sizeof(int)) {
+            ctx->err = "WEAK lists not built by apd_stage_prepare";
+            return APD_ESTATE;
+        }
+        for (int colour = 0; colour < (ctx->weak_per_colour ? 2 : 1); ++colour) {
+            const int n = ctx->weak_per_colour ? ctx->cnt[2 + colour] : nw;
+            const int *wl = ctx->weak_per_colour ? (const int *)list_ptr(ctx, 2 + colour) : (const int *)ctx->wlist.p;
             if (n <= 0) continue;
             // RandomInitialization's kept costs are valid for the first iteration after it only
             Args aw = a;
@@ -5439,7 +5490,7 @@ int32_t apd_stage_iteration(apd_ctx *ctx, int32_t iter) {
                           (ctx->args.tex_f16 ? (ctx->args.sa_any ? wv_lds_bytes<true, 9, true>(a.N, direct) : wv_lds_bytes<true, 9, false>(a.N, direct))
                                              : (ctx->args.sa_any ? wv_lds_bytes<false, 9, true>(a.N, direct) : wv_lds_bytes<false, 9, false>(a.N, direct))),
                           s,
-                          aw, (const int *)list_ptr(ctx, 2 + colour), n, iter, cand, wc);
+                          aw, wl, n, iter, cand, wc, gm);
             prof_end(ctx, e0, APD_PROF_WEAK_SWEEP, n);
         }
         prof_end(ctx, ewp, APD_PROF_WEAK_PATH, ctx->cnt[2] + ctx->cnt[3]);
