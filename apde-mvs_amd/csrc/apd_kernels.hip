@@ -2060,6 +2060,99 @@ __device__ __forceinline__ AncRecV<F16> load_anc_rec(const Args &a, int q, int f
     return R;
 }
 
+// The head of an NCC-New evaluation: the plane's homography into view s, whether the lane's pixel
+// projects into the view (`alive`), and -- BOX -- whether window_rcp_ok_box holds over the pixel's
+// anchor bounding box.
+struct NccNewHead {
+    Hom Hm;
+    bool alive, box_ok;
+};
+template <bool F16, bool SA, bool BOX, int NWIN>
+__device__ __forceinline__ NccNewHead ncc_new_head(const Args &a, const WvRefT<F16, NWIN, SA> &L, int p, int px, int py, int s,
+                                                   float4 pl, bool want) {
+    NccNewHead hd;
+    hd.Hm = homography(a, s, pl);
+    float ptx, pty;
+    project(hd.Hm, (float)px, (float)py, ptx, pty);
+    hd.alive = want && !(ptx >= (float)a.W || ptx < 0.0f || pty >= (float)a.H || pty < 0.0f);
+    hd.box_ok = false;
+    if constexpr (BOX) {
+        const uint32_t b0 = L.box[p], b1 = L.box[VM_P + p];
+        hd.box_ok = hd.alive && window_rcp_ok_box(hd.Hm, (float)((int)(b0 & 0xFFFFu) - 5), (float)((int)(b0 >> 16) - 5),
+                                                  (float)((int)(b1 & 0xFFFFu) + 5), (float)((int)(b1 >> 16) + 5));
+    }
+    return hd;
+}
+// a window anchor's projection (project()'s value)
+template <bool BOX>
+__device__ __forceinline__ void project_anchor(const Hom &Hm, int ax, int ay, bool box_ok, float &asx, float &asy) {
+    if constexpr (BOX) {
+        // the anchor lies in the proven box: rcp_newton(Z) is the correctly rounded 1 / Z there,
+        // so X * it is project()'s value without the IEEE division (lanes outside the proof
+        // take the division)
+        const float X = fmaf(Hm.h[1], (float)ay, fmaf(Hm.h[0], (float)ax, Hm.h[2]));
+        const float Y = fmaf(Hm.h[4], (float)ay, fmaf(Hm.h[3], (float)ax, Hm.h[5]));
+        const float Z = fmaf(Hm.h[7], (float)ay, fmaf(Hm.h[6], (float)ax, Hm.h[8]));
+        float iz = rcp_newton(Z);
+        if (__builtin_amdgcn_ballot_w64(!box_ok)) {
+            const float q = 1.0f / Z;
+            if (!box_ok) iz = q;
+        }
+        asx = X * iz;
+        asy = Y * iz;
+    } else {
+        project(Hm, (float)ax, (float)ay, asx, asy);
+    }
+}
+// NCC-New's centre window (k = 0: the 6x6 window at anchor 0) of pixel slot p under the head's
+// homography -> center_cost (0 when the window is unused -- no anchor 0, or its SA label differs --
+// or empty). Anchor 0 projected out of the source image: `dead` (COST_MAX), and the lane is no longer
+// `alive` for the anchor windows. Called converged, by ncc_new_vm and by the Weak sweep's P1'.
+template <bool F16, bool SA, bool BOX, int NWIN, bool PIPE, class TT>
+__device__ __forceinline__ float ncc_new_centre(const Args &a, const WvRefT<F16, NWIN, SA> &L, int p, int px, int py,
+                                                const Hom &Hm, const TT &T, const SrcTex<F16> &Q, bool box_ok, bool &alive,
+                                                bool &dead, uint32_t *nwc) {
+    const int W = a.W, H = a.H;
+    const int pk = L.anc[p];
+    const bool has = alive && pk >= 0 && ((L.flags[p] >> 16) & 1u);
+    const int ax = has ? (pk & 0xFFFF) : px, ay = has ? (pk >> 16) : py;
+    bool live = has;
+    if (has) {
+        float asx, asy;
+        project_anchor<BOX>(Hm, ax, ay, box_ok, asx, asy);
+        if (asx < 0 || asy < 0 || asx >= (float)W || asy >= (float)H) {
+            live = false;
+            dead = true;
+            alive = false;
+        }
+    }
+    if (!__ballot(live)) return 0.0f;
+    bool fast = live && box_ok;
+    if (!BOX || __ballot(live && !box_ok))
+        if (live && !box_ok) fast = window_rcp_ok(Hm, (float)(ax - 5), (float)(ay - 5));
+    float ss = 0.0f, sss = 0.0f, srs = 0.0f;
+    uint64_t m0 = ~0ull;
+    if constexpr (SA) m0 = L.tmask0[p];
+    ncc_new_window<F16, 6, 2, PIPE>(a, &L.rref[p], VM_P, m0, Hm, ax, ay, live, fast, T, Q, ss, sss, srs);
+    float inv = 1.0f / 36.0f;  // (wv_build_window's 1 / wsum over the 36 taps)
+    if constexpr (SA) inv = L.inv_lut[__builtin_popcountll(m0)];
+    if (!live) return 0.0f;
+    if (nwc) ++*nwc;  // (profiling: windows evaluated)
+    if (inv == 0.0f) return 0.0f;  // (empty window)
+    return ncc_finalize_pre(inv, L.wsrp[p], L.wvar[p], ss, sss, srs);
+}
+// The centre window alone (the Weak sweep's P1': the anchor candidates' centre costs, whose focal terms
+// come from the pair table): ncc_new_vm's statements up to its anchor windows.
+template <bool F16, bool SA, bool BOX, int NWIN, bool PIPE>
+__device__ __forceinline__ float ncc_new_vm_centre(const Args &a, const WvRefT<F16, NWIN, SA> &L, int p, int px, int py, int s,
+                                                   float4 pl, bool want, bool &dead, uint32_t *nwc) {
+    using TT = FastTex<F16, true>;
+    NccNewHead hd = ncc_new_head<F16, SA, BOX, NWIN>(a, L, p, px, py, s, pl, want);
+    const TT T(a, s);
+    const SrcTex<F16> Q(a, s);
+    dead = !hd.alive;
+    return ncc_new_centre<F16, SA, BOX, NWIN, PIPE>(a, L, p, px, py, hd.Hm, T, Q, hd.box_ok, hd.alive, dead, nwc);
+}
 // ComputeBilateralNCCNew + Softmax focal weighting (APD.cu:448-593, 431-446) for pixel slot p, source
 // view s, plane pl, with the reference side from WvLds. Called by every lane of the wave (converged);
 // `want` = the lane evaluates this task. Same operations, in the same order, as ncc_new. `seldep`
@@ -2075,66 +2168,40 @@ __device__ __forceinline__ float ncc_new_vm(const Args &a, const WvRefT<F16, NWI
                                             uint32_t *nwa = nullptr) {
     using TT = FastTex<F16, true>;  // (FastTexD measured 9 % slower in the Weak sweep: twice the texel footprint)
     const int W = a.W, H = a.H;
-    const Hom Hm = homography(a, s, pl);
-    float ptx, pty;
-    project(Hm, (float)px, (float)py, ptx, pty);
-    bool alive = want && !(ptx >= (float)W || ptx < 0.0f || pty >= (float)H || pty < 0.0f);
+    const NccNewHead hd = ncc_new_head<F16, SA, BOX, NWIN>(a, L, p, px, py, s, pl, want);
+    const Hom &Hm = hd.Hm;
+    bool alive = hd.alive;
+    const bool box_ok = hd.box_ok;
     const TT T(a, s);
     const SrcTex<F16> Q(a, s);
     const uint32_t awin = (L.flags[p] >> 16) & 0x1FFu;
     float sc[9];
     int ns = 0;
-    float center_cost = 0.0f, strong_weight = 0.0f;
+    float strong_weight = 0.0f;
     bool dead = !alive;  // COST_MAX (centre or centre-anchor projected out of the image)
-    bool box_ok = false;
-    if constexpr (BOX) {
-        const uint32_t b0 = L.box[p], b1 = L.box[VM_P + p];
-        box_ok = alive && window_rcp_ok_box(Hm, (float)((int)(b0 & 0xFFFFu) - 5), (float)((int)(b0 >> 16) - 5),
-                                            (float)((int)(b1 & 0xFFFFu) + 5), (float)((int)(b1 >> 16) + 5));
-    }
+    const float center_cost = ncc_new_centre<F16, SA, BOX, NWIN, PIPE>(a, L, p, px, py, Hm, T, Q, box_ok, alive, dead, nwc);
 #pragma unroll 1
-    for (int k = 0; k < 9; ++k) {
+    for (int k = 1; k < 9; ++k) {
         const int pk = L.anc[k * VM_P + p];
         const bool has = alive && pk >= 0 && ((awin >> k) & 1u);
 #ifdef APD_ABLATE_ANCHOR_LOCAL  // timing-only (wrong values): anchor windows k >= 1 next to the pixel
-        const int ax = has ? (k == 0 ? (pk & 0xFFFF) : min(max(px + 6 * (((k - 1) % 3) - 1), 0), W - 1)) : px;
-        const int ay = has ? (k == 0 ? (pk >> 16) : min(max(py + 6 * (((k - 1) / 3) - 1), 0), H - 1)) : py;
+        const int ax = has ? min(max(px + 6 * (((k - 1) % 3) - 1), 0), W - 1) : px;
+        const int ay = has ? min(max(py + 6 * (((k - 1) / 3) - 1), 0), H - 1) : py;
 #else
         const int ax = has ? (pk & 0xFFFF) : px, ay = has ? (pk >> 16) : py;
 #endif
         bool live = has;
         if (has) {
             float asx, asy;
-            if constexpr (BOX) {
-                // the anchor lies in the proven box: rcp_newton(Z) is the correctly rounded 1 / Z there,
-                // so X * it is project()'s value without the IEEE division (lanes outside the proof
-                // take the division)
-                const float X = fmaf(Hm.h[1], (float)ay, fmaf(Hm.h[0], (float)ax, Hm.h[2]));
-                const float Y = fmaf(Hm.h[4], (float)ay, fmaf(Hm.h[3], (float)ax, Hm.h[5]));
-                const float Z = fmaf(Hm.h[7], (float)ay, fmaf(Hm.h[6], (float)ax, Hm.h[8]));
-                float iz = rcp_newton(Z);
-                if (__builtin_amdgcn_ballot_w64(!box_ok)) {
-                    const float q = 1.0f / Z;
-                    if (!box_ok) iz = q;
-                }
-                asx = X * iz;
-                asy = Y * iz;
-            } else {
-                project(Hm, (float)ax, (float)ay, asx, asy);
-            }
+            project_anchor<BOX>(Hm, ax, ay, box_ok, asx, asy);
             if (asx < 0 || asy < 0 || asx >= (float)W || asy >= (float)H) {
                 live = false;
-                if (k != 0) {
-                    if (seldep) *seldep = true;
-                    if ((a.sel[ax + ay * W] >> (s - 1)) & 1u) {
+                if (seldep) *seldep = true;
+                if ((a.sel[ax + ay * W] >> (s - 1)) & 1u) {
 #pragma unroll
-                        for (int t = 0; t < 9; ++t) if (t == ns) sc[t] = APD_COST_MAX;
-                        ns++;
-                        strong_weight += 1.0f;
-                    }
-                } else {
-                    dead = true;
-                    alive = false;
+                    for (int t = 0; t < 9; ++t) if (t == ns) sc[t] = APD_COST_MAX;
+                    ns++;
+                    strong_weight += 1.0f;
                 }
             }
         }
@@ -2143,34 +2210,20 @@ __device__ __forceinline__ float ncc_new_vm(const Args &a, const WvRefT<F16, NWI
         if (!BOX || __ballot(live && !box_ok))
             if (live && !box_ok) fast = window_rcp_ok(Hm, (float)(ax - 5), (float)(ay - 5));
         float ss = 0.0f, sss = 0.0f, srs = 0.0f;
-        float inv, srp, var;
-        if (k == 0) {
-            uint64_t m0 = ~0ull;
-            if constexpr (SA) m0 = L.tmask0[p];
-            ncc_new_window<F16, 6, 2, PIPE>(a, &L.rref[p], VM_P, m0, Hm, ax, ay, live, fast, T, Q, ss, sss, srs);
-            inv = 1.0f / 36.0f;  // (wv_build_window's 1 / wsum over the 36 taps)
-            if constexpr (SA) inv = L.inv_lut[__builtin_popcountll(m0)];
-            srp = L.wsrp[p]; var = L.wvar[p];
-        } else {
-            uint64_t mk = 0x1FFull;
-            if constexpr (SA) mk = L.tmask[(k - 1) * VM_P + p];
-            ncc_new_window<F16, 3, 5>(a, &L.rref[(36 + 9 * (k - 1)) * VM_P + p], VM_P, mk, Hm, ax, ay, live, fast, T, Q, ss, sss, srs);
-            inv = 1.0f / 9.0f;
-            if constexpr (SA) inv = L.inv_lut[__builtin_popcount((uint32_t)mk)];
-            srp = L.wsrp[k * VM_P + p]; var = L.wvar[k * VM_P + p];
-        }
+        uint64_t mk = 0x1FFull;
+        if constexpr (SA) mk = L.tmask[(k - 1) * VM_P + p];
+        ncc_new_window<F16, 3, 5>(a, &L.rref[(36 + 9 * (k - 1)) * VM_P + p], VM_P, mk, Hm, ax, ay, live, fast, T, Q, ss, sss, srs);
+        float inv = 1.0f / 9.0f;
+        if constexpr (SA) inv = L.inv_lut[__builtin_popcount((uint32_t)mk)];
+        const float srp = L.wsrp[k * VM_P + p], var = L.wvar[k * VM_P + p];
         if (!live) continue;
-        if (nwc) { if (k == 0) ++*nwc; else ++*nwa; }  // (profiling: windows evaluated)
+        if (nwa) ++*nwa;  // (profiling: windows evaluated)
         if (inv == 0.0f) continue;  // (empty window)
         const float c = ncc_finalize_pre(inv, srp, var, ss, sss, srs);
-        if (k == 0) {
-            center_cost = c;
-        } else {
 #pragma unroll
-            for (int t = 0; t < 9; ++t) if (t == ns) sc[t] = c;
-            ns++;
-            strong_weight += 1.0f;
-        }
+        for (int t = 0; t < 9; ++t) if (t == ns) sc[t] = c;
+        ns++;
+        strong_weight += 1.0f;
     }
     if (dead) return APD_COST_MAX;
     if (strong_weight <= 1e-6f) return center_cost;
@@ -2208,14 +2261,50 @@ __device__ __forceinline__ float ncc_new_vm(const Args &a, const WvRefT<F16, NWI
 #define WV_P2_GEOM_BATCH 0
 #endif
 #define WV_BLOCK (WV_WAVES * WAVE)
-// The anchor candidates' costs (k_weak_cand_g writes, k_weak_cand_comb combines in place, the Weak
-// sweep's P2a reads). gm: [group][view][candidate][VM_P] by the position li in the dense WEAK list, the
+// The anchor candidates' costs (k_weak_cand_g writes the centre costs, k_weak_cand_comb combines in
+// place, the Weak sweep's P2a reads; APD_CAND_CENTRE_IN_SWEEP=1: k_weak_cand_comb writes the focal
+// terms, the sweep's P1' finishes them in place with the centre windows, its P2a reads). gm: [group][view][candidate][VM_P] by the position li in the dense WEAK list, the
 // same 64-entry groups in all three kernels, so a group's N * 8 segments are one contiguous block; else
 // [view][candidate][WEAK index wi] (segments wc * 4 B apart; the per-colour sweep, whose groups are not
 // the candidate kernels').
 __device__ __forceinline__ size_t cand_at(bool gm, int N, int v, int h, int wc, int wi, int li) {
     return gm ? ((size_t)(li / VM_P) * (size_t)(N * 8) + (size_t)(v * 8 + h)) * VM_P + (size_t)(li % VM_P)
               : ((size_t)v * 8 + h) * (size_t)wc + (size_t)wi;
+}
+// The focal combination (APD.cu:576-593, Softmax 431-446) of one (pixel, candidate, view) in two
+// steps -- ncc_new_vm's tail, the same statements in the same order. gp_focal: the softmax-weighted
+// sum `acc` (>= 0, clamped to COST_MAX) of the 8 windows' pair costs sc[k] (< 0: window absent), in
+// anchor order, or GP_NO_FOCAL when no window counts. gp_final: the candidate's cost from the centre
+// window's outcome and that term.
+#define GP_NO_FOCAL (-1.0f)
+__device__ __forceinline__ float gp_focal(const float (&sc)[8]) {
+    uint32_t pm = 0;
+    float strong_weight = 0.0f;
+#pragma unroll
+    for (int k = 0; k < 8; ++k)
+        if (sc[k] >= 0.0f) { pm |= 1u << k; strong_weight += 1.0f; }
+    if (strong_weight <= 1e-6f) return GP_NO_FOCAL;
+    float mx = -1e10f;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) if (((pm >> k) & 1u) && sc[k] > mx) mx = sc[k];
+    float e[8];
+    float sum = 0.0f;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        e[k] = 0.0f;
+        if ((pm >> k) & 1u) { e[k] = d_expf(sc[k] - mx); sum += e[k]; }
+    }
+    float acc = 0.0f;
+#pragma unroll
+    for (int k = 0; k < 8; ++k)
+        if ((pm >> k) & 1u) { const float w = e[k] / sum; acc = fmaf(w, sc[k], acc); }
+    acc = (acc > APD_COST_MAX) ? APD_COST_MAX : acc;
+    return acc;
+}
+__device__ __forceinline__ float gp_final(bool dead, float centre_cost, float acc) {
+    if (dead) return APD_COST_MAX;
+    if (acc < 0.0f) return centre_cost;
+    return (float)(0.25 * (double)centre_cost + 0.75 * (double)acc);
 }
 template <bool F16, bool SA> struct WvOcc {
 #ifdef WV_LDS_OCC
@@ -2227,13 +2316,17 @@ template <bool F16, bool SA> struct WvOcc {
 };
 template <bool F16, bool SA>
 __global__ __launch_bounds__(WV_BLOCK, (WvOcc<F16, SA>::occ)) void k_sweep_weak_vm(Args a, const int *__restrict__ list, int count,
-                                                                int iter, const float *__restrict__ cand, int wc, int gm) {
+                                                                int iter, float *cand, int wc, int gm, int centre_in_sweep) {
     const int N = a.N, W = a.W;
     constexpr bool PIPE = WvOcc<F16, SA>::pipe;
     PHASE_BEGIN;
     // direct: the pair-table kernels evaluated every pixel's anchor candidates, so P2 reads their
     // costs from `cand`; without them (cand == nullptr: APD_NO_CAND_PAIRS=1 or a pair table that does
-    // not fit) P1 evaluates the candidates here (the cost table's rows: wv_cost_rows)
+    // not fit) P1 evaluates the candidates here (the cost table's rows: wv_cost_rows).
+    // centre_in_sweep (direct only): `cand` arrives with the focal terms alone (k_weak_cand_comb's
+    // gp_focal) and P1' evaluates the candidates' centre windows and finishes the costs in place. The
+    // workgroup writes and then reads its own pixels' entries only (hence no const / __restrict__ on
+    // `cand`: the loads of P2a stay behind the stores of P1' and the barrier between them).
     const bool direct = cand != nullptr;
     WvLdsT<F16, 9, SA> &L = *reinterpret_cast<WvLdsT<F16, 9, SA> *>(apd_dyn_lds);
     wv_init_lut(L);  // (read after P0's barrier)
@@ -2357,8 +2450,30 @@ __global__ __launch_bounds__(WV_BLOCK, (WvOcc<F16, SA>::occ)) void k_sweep_weak_
         if (want) val = nv;
         costL[t * VM_P + p1] = val;
     }
+    // ---- P1' (direct, centre_in_sweep): the anchor candidates' centre windows, (view, candidate)
+    // tasks dealt as P1's, lane = pixel. P0 built the centre window's reference side and L.hyp holds
+    // the candidates' planes; the focal term of (pixel, candidate, view) waits at its place in `cand`
+    // and gp_final leaves the candidate's cost there for P2a. (Measured at C3: the phase adds what
+    // k_weak_cand_g took alone, it does not hide behind the other workgroups' gathers)
+    uint32_t nwp = 0;  // profiling: the candidates' centre windows this lane evaluated
+    if (direct && centre_in_sweep) {
+        const int wi1 = gm ? 0 : a.amap[c1];
+        for (int u = wave; u < 8 * N; u += WV_WAVES) {
+            const int v = u / 8, h = u - 8 * v;
+            const bool want = pv1 && ((L.flags[p1] >> h) & 1u);
+            if (!__ballot(want)) continue;
+            const float4 pl = L.hyp[h * VM_P + p1];
+            bool dead;
+            const float cc = ncc_new_vm_centre<F16, SA, true, 9, PIPE>(a, L, p1, px1, py1, v + 1, pl, want, dead, &nwp);
+            if (want) {
+                float *o = cand + cand_at(gm != 0, N, v, h, wc, wi1, first + p1);
+                *o = gp_final(dead, cc, *o);
+            }
+        }
+    }
     __syncthreads();
-    PHASE_STAMP(1);
+    if (direct && centre_in_sweep) PHASE_STAMP(23);  // (instrumented builds: P1' apart from P1)
+    else PHASE_STAMP(1);
 
     // ---- P2a: lane = (pixel, view) groups: view selection, the anchor hypotheses' weighted costs
     // (with their geometric terms) and their argmin
@@ -2761,15 +2876,16 @@ __global__ __launch_bounds__(WV_BLOCK, (WvOcc<F16, SA>::occ)) void k_sweep_weak_
         if (lane == 0) { atomicAdd(PROF_AT(a.evals, 1), (unsigned long long)nn); atomicAdd(PROF_AT(a.evals, 2), (unsigned long long)ng); }
     }
     if (a.evals) {  // ... plus the fit-plane and refinement evaluations every wave issued (P3, P5)
-        uint32_t nn = issued_nn, ng = issued_g, wc0 = nwc, wa0 = nwa;
+        uint32_t nn = issued_nn, ng = issued_g, wc0 = nwc, wa0 = nwa, wp0 = nwp;
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) {
             nn += __shfl_xor(nn, o); ng += __shfl_xor(ng, o);
-            wc0 += __shfl_xor(wc0, o); wa0 += __shfl_xor(wa0, o);
+            wc0 += __shfl_xor(wc0, o); wa0 += __shfl_xor(wa0, o); wp0 += __shfl_xor(wp0, o);
         }
         if (lane == 0) {
             atomicAdd(PROF_AT(a.evals, 1), (unsigned long long)nn); atomicAdd(PROF_AT(a.evals, 2), (unsigned long long)ng);
             atomicAdd(PROF_AT(a.evals, 7), (unsigned long long)wc0); atomicAdd(PROF_AT(a.evals, 8), (unsigned long long)wa0);
+            if (wp0) atomicAdd(PROF_AT(a.evals, 6), (unsigned long long)wp0);  // (P1': the candidates' centre windows)
         }
     }
 
@@ -2829,8 +2945,10 @@ __global__ __launch_bounds__(WV_BLOCK, (WvOcc<F16, SA>::occ)) void k_sweep_weak_
 //     differ between runs, the costs never do.
 //   per iteration: k_gp_cost evaluates every pair in every view (lane = pair, consecutive pairs share
 //     a window anchor) into pcost[pair][view]; k_weak_cand_g evaluates the centre windows (lane =
-//     pixel, wave = candidate) and the focal combination reading the pair costs, and writes the same
-//     costs the sweep reads (direct mode; layout: cand_at).
+//     pixel, wave = candidate) and k_weak_cand_comb the focal combination reading the pair costs, and
+//     writes the same costs the sweep reads (direct mode; layout: cand_at).
+//     APD_CAND_CENTRE_IN_SWEEP=1: k_weak_cand_comb writes the focal term alone and the Weak sweep
+//     evaluates the centre windows (P1') and finishes the costs in place.
 // ---------------------------------------------------------------------------------------------
 #ifndef GP_CHUNK
 #define GP_CHUNK 256   // references per batch of k_gp_dedup (one workgroup per window anchor)
@@ -3379,33 +3497,11 @@ __global__ __launch_bounds__(BLOCK) void k_gp_cost(Args a, const int2 *__restric
 // order -- ncc_new_vm's statements
 __device__ __forceinline__ float gp_combine(float cc, const float (&sc)[8]) {
     if (cc < 0.0f) return APD_COST_MAX;
-    const float center_cost = cc;
-    uint32_t pm = 0;
-    float strong_weight = 0.0f;
-#pragma unroll
-    for (int k = 0; k < 8; ++k)
-        if (sc[k] >= 0.0f) { pm |= 1u << k; strong_weight += 1.0f; }
-    if (strong_weight <= 1e-6f) return center_cost;
-    float mx = -1e10f;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) if (((pm >> k) & 1u) && sc[k] > mx) mx = sc[k];
-    float e[8];
-    float sum = 0.0f;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        e[k] = 0.0f;
-        if ((pm >> k) & 1u) { e[k] = d_expf(sc[k] - mx); sum += e[k]; }
-    }
-    float acc = 0.0f;
-#pragma unroll
-    for (int k = 0; k < 8; ++k)
-        if ((pm >> k) & 1u) { const float w = e[k] / sum; acc = fmaf(w, sc[k], acc); }
-    acc = (acc > APD_COST_MAX) ? APD_COST_MAX : acc;
-    return (float)(0.25 * (double)center_cost + 0.75 * (double)acc);
+    return gp_final(false, cc, gp_focal(sc));
 }
 
-// the anchor candidates' centre windows (k_weak_cand_comb then combines them with the pair costs);
-// lane = pixel, wave = candidate h. Per view (the waves take the views together: one source image,
+// the anchor candidates' centre windows (k_weak_cand_comb then combines them with the pair costs;
+// not launched under APD_CAND_CENTRE_IN_SWEEP=1, where the Weak sweep's P1' does this work); lane = pixel, wave = candidate h. Per view (the waves take the views together: one source image,
 // the CU's L1) the centre window of (pixel, h) -> out at cand_at (-1: dead, the pixel or its
 // anchor 0 projected out of frame). With an SA label at the pixel the centre window is used only
 // when anchor 0 carries the label (else center_cost stays 0, APD.cu:493-497) and its taps are
@@ -3525,7 +3621,9 @@ __global__ __launch_bounds__(PK_BLOCK, PK_MINW) void k_weak_cand_g(Args a, const
 // The focal combination (APD.cu:576-593, Softmax 431-446) of each (WEAK pixel, candidate) and view,
 // a thread per (pixel, candidate): few registers and many waves in flight for the pair-cost gathers.
 // `out` holds the centre cost (< 0: dead) and receives the candidate's cost in its place; the pixel's
-// used windows (wmw) say which of its 8 pair ids exist. Block = 4 candidates x 64 pixels of one group.
+// used windows (wmw) say which of its 8 pair ids exist. focal_only (the centre windows are the Weak
+// sweep's): `out` is not read and receives the focal term alone (gp_focal), which the sweep's P1'
+// finishes in place. Block = 4 candidates x 64 pixels of one group.
 // The block's pair ids ([WEAK index][window k][candidate h], 4 candidates = one 16-byte chunk per
 // (pixel, k)) are staged in LDS with 16-byte loads of whole chunks first: a thread's 8 ids lie 32 B
 // apart and the wave's 64 pixels 256 B apart, so loading them per thread issued 8 scattered 4-byte
@@ -3534,7 +3632,8 @@ __global__ __launch_bounds__(PK_BLOCK, PK_MINW) void k_weak_cand_g(Args a, const
 __global__ __launch_bounds__(BLOCK) void k_weak_cand_comb(Args a, const int *__restrict__ list, int count,
                                                           const uint8_t *__restrict__ cbw, const uint8_t *__restrict__ wmw,
                                                           const uint32_t *__restrict__ pidx,
-                                                          const float *__restrict__ pcost, float *__restrict__ out, int wc, int gm) {
+                                                          const float *__restrict__ pcost, float *__restrict__ out, int wc, int gm,
+                                                          int focal_only) {
     __shared__ uint32_t sid[VM_P * COMB_STRIDE];
     const int b = xcd_remap(blockIdx.x, gridDim.x);
     const int h0 = (b & 1) << 2, hl = threadIdx.x >> 6, h = h0 + hl;
@@ -3574,7 +3673,7 @@ __global__ __launch_bounds__(BLOCK) void k_weak_cand_comb(Args a, const int *__r
 #pragma unroll
             for (int k = 0; k < 8; ++k) sc[k] = dv == 0 ? q[k].x : dv == 1 ? q[k].y : dv == 2 ? q[k].z : q[k].w;
             float *o = out + cand_at(gm != 0, N, v, h, wc, wi, i);
-            *o = gp_combine(*o, sc);
+            *o = focal_only ? gp_focal(sc) : gp_combine(*o, sc);
         }
     }
 }
@@ -4407,6 +4506,8 @@ struct apd_ctx {
                                    // strips (no fewer distinct anchors per group: profiles/weak_group_sharing.txt)
     bool cand_gm = true;           // the candidates' costs as [group][view][candidate][64]; APD_NO_CAND_GROUP_MAJOR=1 (and
                                    // the per-colour sweep): [view][candidate][WEAK index]
+    bool centre_in_sweep = false;  // APD_CAND_CENTRE_IN_SWEEP=1: the candidates' centre windows in the Weak sweep's P1'
+                                   // instead of k_weak_cand_g (measured slower at C3; A/B, parity)
     bool gp_on = false;            // the pair table of the prepared problem is built (apd_stage_prepare)
     bool ga_split = true;          // GenAnchors' RANSAC in k_gen_anchors_fit; APD_NO_GA_SPLIT=1: in k_gen_anchors
     bool rec_on = false;           // the anchor-window records of the prepared problem are built (k_anchor_rec)
@@ -4660,6 +4761,7 @@ apd_ctx *apd_create(int32_t device) {
     ctx->weak_per_colour = getenv("APD_WEAK_PER_COLOUR") != nullptr;
     ctx->weak_quad = getenv("APD_WEAK_QUAD") != nullptr;
     ctx->cand_gm = getenv("APD_NO_CAND_GROUP_MAJOR") == nullptr && !ctx->weak_per_colour;
+    ctx->centre_in_sweep = getenv("APD_CAND_CENTRE_IN_SWEEP") != nullptr;
     ctx->ga_split = getenv("APD_NO_GA_SPLIT") == nullptr;
     ctx->lr_handover = getenv("APD_NO_LR_HANDOVER") == nullptr;
     ctx->wcur_on = getenv("APD_NO_WCUR") == nullptr;
@@ -5418,14 +5520,19 @@ int32_t apd_stage_iteration(apd_ctx *ctx, int32_t iter) {
     if (a.use_apd) {
         // the Weak path's wall time (RANSAC beside the candidate kernels, then the Weak sweeps)
         hipEvent_t ewp = prof_begin(ctx);
-        // fork: RANSAC (side stream 0) and k_gp_cost (side stream 1) beside k_weak_cand_g (ctx stream)
+        // fork: RANSAC (side stream 0) and k_gp_cost (side stream 1) beside k_weak_cand_g (ctx stream),
+        // then k_weak_cand_comb. APD_CAND_CENTRE_IN_SWEEP=1: RANSAC beside k_gp_cost and
+        // k_weak_cand_comb (ctx stream); the candidates' centre windows are the Weak sweep's P1'.
+        const bool centre_kernel = !ctx->centre_in_sweep;
         hipStream_t sr = s, sg = s;
         if (ctx->overlap) {
             HIP_OK(ctx, hipEventRecord(ctx->ev_fork, s));
             HIP_OK(ctx, hipStreamWaitEvent(ctx->side[0], ctx->ev_fork, 0));
-            HIP_OK(ctx, hipStreamWaitEvent(ctx->side[1], ctx->ev_fork, 0));
             sr = ctx->side[0];
-            sg = ctx->side[1];
+            if (centre_kernel) {
+                HIP_OK(ctx, hipStreamWaitEvent(ctx->side[1], ctx->ev_fork, 0));
+                sg = ctx->side[1];
+            }
         }
         hipEvent_t e0 = prof_begin(ctx, sr);
         hipLaunchKernelGGL(k_ransac_fit, dim3(blocks_for((size_t)a.HW, BLOCK)), dim3(BLOCK), 0, sr, a, iter);
@@ -5433,7 +5540,7 @@ int32_t apd_stage_iteration(apd_ctx *ctx, int32_t iter) {
         if (ctx->overlap) HIP_OK(ctx, hipEventRecord(ctx->ev_side[0], sr));
         const int nw = ctx->cnt[2] + ctx->cnt[3];
         const int wc = std::max(ctx->weak_count, 1);
-        const float *cand = nullptr;
+        float *cand = nullptr;  // (the Weak sweep finishes the candidates' costs in place unless centre_kernel)
         const int gm = ctx->cand_gm ? 1 : 0;  // the candidates' costs by the dense list's groups (cand_at)
         if (ctx->cand_pairs && nw > 0 && ctx->gp_on) {
             if (ctx->wcand.bytes < wcand_bytes(a.N, (size_t)wc, nw) || ctx->wlist.bytes < (size_t)nw * sizeof(int)) {
@@ -5448,19 +5555,22 @@ int32_t apd_stage_iteration(apd_ctx *ctx, int32_t iter) {
                     LAUNCH_TEX_SA(k_gp_cost, dim3(blocks_for((size_t)ctx->gp_np, BLOCK)), dim3(BLOCK), gp_cost_lds_bytes(a.N), sg, ac,
                                (const int2 *)ctx->gp_plist.p, ctx->gp_np, (float *)ctx->gp_pcost.p);
                 prof_end(ctx, e1, APD_PROF_GP_COST, ctx->gp_np, sg);
-                if (ctx->overlap) HIP_OK(ctx, hipEventRecord(ctx->ev_side[1], sg));
-                e1 = prof_begin(ctx);
-                LAUNCH_TEX_SA(k_weak_cand_g, dim3(blocks_for((size_t)nw, VM_P)), dim3(PK_BLOCK), 0, s, ac, (const int *)ctx->wlist.p, nw,
-                              (const uint8_t *)ctx->gp_cb.p, (float *)ctx->wcand.p, wc, gm);
-                prof_end(ctx, e1, APD_PROF_WEAK_CAND_G, nw);
-                if (ctx->overlap) HIP_OK(ctx, hipStreamWaitEvent(s, ctx->ev_side[1], 0));  // join k_gp_cost
+                if (centre_kernel) {
+                    if (ctx->overlap) HIP_OK(ctx, hipEventRecord(ctx->ev_side[1], sg));
+                    e1 = prof_begin(ctx);
+                    LAUNCH_TEX_SA(k_weak_cand_g, dim3(blocks_for((size_t)nw, VM_P)), dim3(PK_BLOCK), 0, s, ac, (const int *)ctx->wlist.p, nw,
+                                  (const uint8_t *)ctx->gp_cb.p, (float *)ctx->wcand.p, wc, gm);
+                    prof_end(ctx, e1, APD_PROF_WEAK_CAND_G, nw);
+                    if (ctx->overlap) HIP_OK(ctx, hipStreamWaitEvent(s, ctx->ev_side[1], 0));  // join k_gp_cost
+                }
                 e1 = prof_begin(ctx);
                 hipLaunchKernelGGL(k_weak_cand_comb, dim3(2 * blocks_for((size_t)nw, VM_P)), dim3(BLOCK), 0, s, ac,
                                    (const int *)ctx->wlist.p, nw, (const uint8_t *)ctx->gp_cb.p, (const uint8_t *)ctx->gp_cb.p + wc,
-                                   (const uint32_t *)ctx->gp_pidx.p, (const float *)ctx->gp_pcost.p, (float *)ctx->wcand.p, wc, gm);
+                                   (const uint32_t *)ctx->gp_pidx.p, (const float *)ctx->gp_pcost.p, (float *)ctx->wcand.p, wc, gm,
+                                   centre_kernel ? 0 : 1);
                 prof_end(ctx, e1, APD_PROF_WEAK_CAND_COMB, nw);
             }
-            cand = (const float *)ctx->wcand.p;
+            cand = (float *)ctx->wcand.p;
         }
         if (ctx->overlap) HIP_OK(ctx, hipStreamWaitEvent(s, ctx->ev_side[0], 0));  // join RANSAC (the sweep reads a.fit)
         // One Weak launch over the dense two-colour list. The checkerboard buys nothing here: for a
@@ -5469,8 +5579,9 @@ int32_t apd_stage_iteration(apd_ctx *ctx, int32_t iter) {
         // 0 is the pixel itself), and it writes a.plane, a.cost, a.sel and a.vw at WEAK pixels only.
         // No anchor 1..8 is a WEAK pixel, so nothing one workgroup writes is read by another: the
         // anchors' entries were last written by the Strong sweeps, earlier on this stream, and a.fit by
-        // the RANSAC joined above. The source views, a.depth and the candidates' costs are read-only
-        // here. APD_WEAK_PER_COLOUR=1 keeps the launch per colour over the per-colour lists.
+        // the RANSAC joined above. The source views and a.depth are read-only here, and of the
+        // candidates' costs a workgroup touches its own pixels' entries only (P1' finishes them in
+        // place under APD_CAND_CENTRE_IN_SWEEP=1; otherwise they are read-only too). APD_WEAK_PER_COLOUR=1 keeps the launch per colour over the per-colour lists.
         if (!ctx->weak_per_colour && nw > 0 && ctx->wlist.bytes < (size_t)nw * sizeof(int)) {
             ctx->err = "WEAK lists not built by apd_stage_prepare";
             return APD_ESTATE;
@@ -5490,7 +5601,7 @@ int32_t apd_stage_iteration(apd_ctx *ctx, int32_t iter) {
                           (ctx->args.tex_f16 ? (ctx->args.sa_any ? wv_lds_bytes<true, 9, true>(a.N, direct) : wv_lds_bytes<true, 9, false>(a.N, direct))
                                              : (ctx->args.sa_any ? wv_lds_bytes<false, 9, true>(a.N, direct) : wv_lds_bytes<false, 9, false>(a.N, direct))),
                           s,
-                          aw, wl, n, iter, cand, wc, gm);
+                          aw, wl, n, iter, cand, wc, gm, (direct && !centre_kernel) ? 1 : 0);
             prof_end(ctx, e0, APD_PROF_WEAK_SWEEP, n);
         }
         prof_end(ctx, ewp, APD_PROF_WEAK_PATH, ctx->cnt[2] + ctx->cnt[3]);
@@ -5702,14 +5813,15 @@ int32_t apd_profile_kernel(apd_ctx *ctx, int32_t kind, double *ms_total, int64_t
     double tot = 0.0;
     int64_t nl = 0, px = 0;
     for (auto &pe : ctx->prof_ev) {
-        // APD_PROF_WEAK_CAND: the three candidate kernels together (one launch = one k_weak_cand_g)
+        // APD_PROF_WEAK_CAND: the candidate kernels together (one launch = one k_weak_cand_g, or one
+        // k_weak_cand_comb where APD_CAND_CENTRE_IN_SWEEP=1 leaves k_weak_cand_g out)
         const bool sub = kind == APD_PROF_WEAK_CAND &&
                          (pe.kind == APD_PROF_GP_COST || pe.kind == APD_PROF_WEAK_CAND_G || pe.kind == APD_PROF_WEAK_CAND_COMB);
         if (pe.kind != kind && !sub) continue;
         float ms = 0.0f;
         (void)hipEventElapsedTime(&ms, pe.e0, pe.e1);
         tot += ms;
-        if (!sub || pe.kind == APD_PROF_WEAK_CAND_G) {
+        if (!sub || pe.kind == (ctx->centre_in_sweep ? APD_PROF_WEAK_CAND_COMB : APD_PROF_WEAK_CAND_G)) {
             ++nl;
             px += pe.px;
         }
