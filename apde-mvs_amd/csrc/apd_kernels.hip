@@ -1689,6 +1689,9 @@ __global__ __launch_bounds__(VM_BLOCK, (SS_LDS40 && F16 && !SA) ? 4 : VM_MINW) v
 //   P4  lane = pixel: fit acceptance, the 5 refinement candidates (RNG continues from P2)
 //   P5  (candidate, view) tasks for views with weight > 0
 //   P6  lane = pixel: acceptance, writes
+// Geometric passes: P3' (before P3) and P5' (after P4) compute the fit plane's / the candidates'
+// geometric terms for all weighted views first, and the exact early exit of P3 / P5 takes them as the
+// tail of its chain (APD_NO_GEOM_TAIL=1 disables).
 // ---------------------------------------------------------------------------------------------
 // NCC-New reference side of a pixel slot (anchors, window taps, SA tap masks, moments): shared by the
 // Weak sweep and RandomInitialization under APD
@@ -2316,7 +2319,8 @@ template <bool F16, bool SA> struct WvOcc {
 };
 template <bool F16, bool SA>
 __global__ __launch_bounds__(WV_BLOCK, (WvOcc<F16, SA>::occ)) void k_sweep_weak_vm(Args a, const int *__restrict__ list, int count,
-                                                                int iter, float *cand, int wc, int gm, int centre_in_sweep) {
+                                                                int iter, float *cand, int wc, int gm, int centre_in_sweep,
+                                                                int geom_tail_on) {
     const int N = a.N, W = a.W;
     constexpr bool PIPE = WvOcc<F16, SA>::pipe;
     PHASE_BEGIN;
@@ -2346,6 +2350,16 @@ __global__ __launch_bounds__(WV_BLOCK, (WvOcc<F16, SA>::occ)) void k_sweep_weak_
     const bool pv1 = p1 < np;
     const int c1 = list[first + min(p1, np - 1)];
     const int py1 = c1 / W, px1 = c1 - py1 * W;
+    // gtail (geometric passes, direct only; APD_NO_GEOM_TAIL=1 disables): the geometric terms of the fit
+    // plane and of the refinement candidates are computed for all weighted views before their windows
+    // (pre-passes before P3 and after P4) and the early exit adds them as the chain's tail (below).
+    // They live in the workgroup's own entries of `cand` -- slot s of (view, pixel) at candidate s's
+    // place, s = 0 the fit plane, 1..5 the refinement candidates: P2a was those entries' last reader
+    // and the candidate kernels rewrite every entry P2a reads in the next iteration before it does.
+    const bool gtail = geom && direct && geom_tail_on != 0;
+    auto gt_at = [&](int v, int s, int p) -> float * {
+        return cand + cand_at(gm != 0, N, v, s, wc, gm ? 0 : a.amap[list[first + p]], first + p);
+    };
 
     // ---- P0: anchors, planes, NCC-New reference data
     if (pv1) {
@@ -2697,7 +2711,31 @@ __global__ __launch_bounds__(WV_BLOCK, (WvOcc<F16, SA>::occ)) void k_sweep_weak_
     __syncthreads();
     // fold the views of slot `s` (cost table row `row`, K tasks per view, candidate k) that the tasks
     // below `done` completed; then flag the slot when its partial cost reaches thr
-    auto fold = [&](int s, int K, int k, int row, int done) {
+    //
+    // The geometric tail (gtail). Every view's cost is c_v = fmaf(gf, g_v, n_v) with the NCC-New term
+    // n_v >= 0 (ncc_new_vm returns APD_COST_MAX or a mean of ncc_finalize_pre's values, clamped to
+    // [0, 2]) and the geometric term g_v known for all weighted views from the pre-pass. fmaf(gf, g, x)
+    // is monotone in x (one rounding of an exact sum; whatever gf's sign), so
+    // l_v = fmaf(gf, g_v, 0.0f) <= c_v; fmaf(w, c, x) with w > 0 is monotone in c and in x, so by
+    // induction the chain T that takes the exact c_v for the views folded so far (T starts at P) and
+    // l_v for the remaining weighted views, in the same view order, never exceeds S; the division by
+    // wn > 0 is monotone. Hence fl(T / wn) >= thr implies fl(S / wn) >= thr: the candidate would have
+    // been rejected anyway, against the same thr, and is flagged now. The tail is also taken once with
+    // P = 0 before the first window is sampled. NaN: a NaN thr or g_v or wn = 0 (0 / 0) makes the
+    // comparison false, nothing is flagged early; a NaN n_v makes S NaN, which P4 / P6 reject in both
+    // versions (tc < cost_now is false), whether or not T flagged the slot before that view. Without
+    // gtail (non-geometric passes, no `cand`) neither the pre-passes nor the tail loops run.
+    // tail of slot s (0 fit, 1..5 candidates) of pixel p from view v on, added to the prefix P
+    auto tail = [&](int s, int p, int v, float P) {
+        float T = P;
+        for (; v < N; ++v) {
+            const int wk = wts[v * VM_P + p];
+            if (wk > 0) T = fmaf((float)wk, fmaf(gf, *gt_at(v, s, p), 0.0f), T);
+        }
+        return T;
+    };
+    // `all`: also the slots without a newly completed view (the fold before the first batch)
+    auto fold = [&](int s, int K, int k, int row, int done, bool all) {
         for (int p = tid; p < VM_P; p += WV_BLOCK) {
             const int it = s * VM_P + p;
             if (dead[it]) continue;
@@ -2708,16 +2746,36 @@ __global__ __launch_bounds__(WV_BLOCK, (WvOcc<F16, SA>::occ)) void k_sweep_weak_
                 const int wk = wts[v * VM_P + p];
                 if (wk > 0) P = fmaf((float)wk, costL[(row + v) * VM_P + p], P);
             }
-            if (v == v0) continue;
+            if (v == v0 && !all) continue;
             nxt[it] = (uint8_t)v;
             part[it] = P;
-            if (P / L.st[3 * VM_P + p] >= L.st[1 * VM_P + p]) dead[it] = 1;
+            float T = P;
+            if (gtail && p < np && (L.flags[p] >> 31)) T = tail(s, p, v, P);
+            if (T / L.st[3 * VM_P + p] >= L.st[1 * VM_P + p]) dead[it] = 1;
         }
     };
 
+    // ---- P3': the fit plane's geometric terms (views with weight > 0), wave = view, lane = pixel; then
+    // the pure tail (no window sampled yet)
+    if (gtail) {
+        for (int v = wave; v < N; v += WV_WAVES) {
+            if (refine && wts[v * VM_P + p1] > 0) {
+                *gt_at(v, 0, p1) = geom_cost(a, px1, py1, v + 1, fit1);
+                ++issued_g;
+            }
+        }
+        __syncthreads();
+        fold(0, 1, 0, 0, 0, true);
+        __syncthreads();
+        PHASE_STAMP(10);  // (instrumented builds: the fit plane's pre-pass apart from P3)
+    }
+
     // ---- P3: fit-plane tasks (views with weight > 0), early exit against the cost after P2
     for (int v0 = 0; v0 < N; v0 += WV_WAVES) {
-        if (v0 > 0) fold(0, 1, 0, 0, v0);
+        if (v0 > 0) fold(0, 1, 0, 0, v0, false);
+        // (gtail: the waves take the batch with the fold's flags; wave 0, which folds, is the batch's
+        // last wave either way)
+        if (v0 > 0 && gtail) __syncthreads();
         const int v = v0 + wave;
         if (v < N) {
             float cv = 0.0f;
@@ -2727,9 +2785,9 @@ __global__ __launch_bounds__(WV_BLOCK, (WvOcc<F16, SA>::occ)) void k_sweep_weak_
             const float nv = ncc_new_vm<F16, SA, true, 9, PIPE>(a, L, p1, px1, py1, v + 1, fit, want, nullptr, &nwc, &nwa);
             if (want) {
                 cv = nv;
-                if (geom) cv = fmaf(gf, geom_cost(a, px1, py1, v + 1, fit), cv);
+                if (gtail) cv = fmaf(gf, *gt_at(v, 0, p1), cv);  // (P3' computed the term)
+                else if (geom) { cv = fmaf(gf, geom_cost(a, px1, py1, v + 1, fit), cv); ++issued_g; }
                 ++issued_nn;
-                issued_g += geom;
             }
             costL[v * VM_P + p1] = cv;
         }
@@ -2786,6 +2844,52 @@ __global__ __launch_bounds__(WV_BLOCK, (WvOcc<F16, SA>::occ)) void k_sweep_weak_
 #pragma unroll
             for (int k = 0; k < 5; ++k) m[k] = __ballot(base && !dead[(1 + k) * VM_P + p1]);
         };
+        // fold views [nxt, v1) of the refining pixels' 5 slots (all threads: slot 1 + i / 64), the batch
+        // [v0, v1) with its views `ne` in the cost table; gtail: then the chain's tail over the views
+        // from v1 on (fold5(0, 0, 0): the pure tail)
+        auto fold5 = [&](int v0, int v1, uint64_t ne) {
+            for (int i = tid; i < 5 * VM_P; i += WV_BLOCK) {
+                const int k = i / VM_P, p = i - k * VM_P, sl = (1 + k) * VM_P + p;
+                if (dead[sl] || !(p < np && (L.flags[p] >> 31))) continue;
+                int v = nxt[sl];
+                float P = part[sl];
+                for (; v < v1; ++v) {
+                    const int wk = wts[v * VM_P + p];
+                    if (wk > 0) P = fmaf((float)wk, costL[(k * VB + __builtin_popcountll(ne & ((1ull << (v - v0)) - 1ull))) * VM_P + p], P);
+                }
+                nxt[sl] = (uint8_t)v;
+                part[sl] = P;
+                const float T = gtail ? tail(1 + k, p, v, P) : P;
+                if (T / L.st[3 * VM_P + p] >= L.st[1 * VM_P + p]) dead[sl] = 1;
+            }
+        };
+        // ---- P5': the candidates' geometric terms (views with weight > 0), wave = view, lane = pixel,
+        // a view's five source-depth gathers in flight together (geom_point / geom_head / geom_tail:
+        // geom_cost's statements); then the pure tail
+        if (gtail) {
+            float Pw[5][3];
+            if (refine) {
+#pragma unroll
+                for (int k = 0; k < 5; ++k) geom_point(a, px1, py1, WV_CAND(L)[k * VM_P + p1], Pw[k]);
+            }
+            for (int v = wave; v < N; v += WV_WAVES) {
+                if (refine && wts[v * VM_P + p1] > 0) {
+                    GeomHead gh[5];
+                    float sdep[5];
+#pragma unroll
+                    for (int k = 0; k < 5; ++k) gh[k] = geom_head(a, v + 1, Pw[k]);
+#pragma unroll
+                    for (int k = 0; k < 5; ++k) sdep[k] = a.depth[gh[k].idx];
+#pragma unroll
+                    for (int k = 0; k < 5; ++k) *gt_at(v, 1 + k, p1) = geom_tail(a, px1, py1, v + 1, gh[k], sdep[k]);
+                    issued_g += 5;
+                }
+            }
+            __syncthreads();
+            fold5(0, 0, 0);
+            __syncthreads();
+            PHASE_STAMP(11);  // (instrumented builds: the candidates' pre-pass apart from P5)
+        }
         for (int v0 = 0; v0 < N;) {
             int v1 = v0, nch = 0, nne = 0;
             uint64_t ne = 0;  // bit v - v0: view v has items
@@ -2829,28 +2933,15 @@ __global__ __launch_bounds__(WV_BLOCK, (WvOcc<F16, SA>::occ)) void k_sweep_weak_
                     const float nv = ncc_new_vm<F16, SA, true, 9, PIPE>(a, L, p, px, py, v + 1, tp, want, nullptr, &nwc, &nwa);
                     if (want) {
                         float cv = nv;
-                        if (geom) cv = fmaf(gf, geom_cost(a, px, py, v + 1, tp), cv);
+                        if (gtail) cv = fmaf(gf, *gt_at(v, 1 + k, p), cv);  // (P5' computed the term)
+                        else if (geom) { cv = fmaf(gf, geom_cost(a, px, py, v + 1, tp), cv); ++issued_g; }
                         ++issued_nn;
-                        issued_g += geom;
                         costL[(k * VB + __builtin_popcountll(ne & ((1ull << (v - v0)) - 1ull))) * VM_P + p] = cv;
                     }
                 }
             }
             __syncthreads();
-            // fold views [nxt, v1) of the refining pixels' 5 slots (all threads: slot 1 + i / 64)
-            for (int i = tid; i < 5 * VM_P; i += WV_BLOCK) {
-                const int k = i / VM_P, p = i - k * VM_P, sl = (1 + k) * VM_P + p;
-                if (dead[sl] || !(p < np && (L.flags[p] >> 31))) continue;
-                int v = nxt[sl];
-                float P = part[sl];
-                for (; v < v1; ++v) {
-                    const int wk = wts[v * VM_P + p];
-                    if (wk > 0) P = fmaf((float)wk, costL[(k * VB + __builtin_popcountll(ne & ((1ull << (v - v0)) - 1ull))) * VM_P + p], P);
-                }
-                nxt[sl] = (uint8_t)v;
-                part[sl] = P;
-                if (P / L.st[3 * VM_P + p] >= L.st[1 * VM_P + p]) dead[sl] = 1;
-            }
+            fold5(v0, v1, ne);
             __syncthreads();
             v0 = v1;
         }
@@ -4508,6 +4599,8 @@ struct apd_ctx {
                                    // the per-colour sweep): [view][candidate][WEAK index]
     bool centre_in_sweep = false;  // APD_CAND_CENTRE_IN_SWEEP=1: the candidates' centre windows in the Weak sweep's P1'
                                    // instead of k_weak_cand_g (measured slower at C3; A/B, parity)
+    bool geom_tail = true;         // the Weak sweep's early exit takes the geometric terms of the views still to come
+                                   // as its tail (geometric passes with the candidates' buffer); APD_NO_GEOM_TAIL=1 disables
     bool gp_on = false;            // the pair table of the prepared problem is built (apd_stage_prepare)
     bool ga_split = true;          // GenAnchors' RANSAC in k_gen_anchors_fit; APD_NO_GA_SPLIT=1: in k_gen_anchors
     bool rec_on = false;           // the anchor-window records of the prepared problem are built (k_anchor_rec)
@@ -4762,6 +4855,7 @@ apd_ctx *apd_create(int32_t device) {
     ctx->weak_quad = getenv("APD_WEAK_QUAD") != nullptr;
     ctx->cand_gm = getenv("APD_NO_CAND_GROUP_MAJOR") == nullptr && !ctx->weak_per_colour;
     ctx->centre_in_sweep = getenv("APD_CAND_CENTRE_IN_SWEEP") != nullptr;
+    ctx->geom_tail = getenv("APD_NO_GEOM_TAIL") == nullptr;
     ctx->ga_split = getenv("APD_NO_GA_SPLIT") == nullptr;
     ctx->lr_handover = getenv("APD_NO_LR_HANDOVER") == nullptr;
     ctx->wcur_on = getenv("APD_NO_WCUR") == nullptr;
@@ -5581,7 +5675,10 @@ int32_t apd_stage_iteration(apd_ctx *ctx, int32_t iter) {
         // anchors' entries were last written by the Strong sweeps, earlier on this stream, and a.fit by
         // the RANSAC joined above. The source views and a.depth are read-only here, and of the
         // candidates' costs a workgroup touches its own pixels' entries only (P1' finishes them in
-        // place under APD_CAND_CENTRE_IN_SWEEP=1; otherwise they are read-only too). APD_WEAK_PER_COLOUR=1 keeps the launch per colour over the per-colour lists.
+        // place under APD_CAND_CENTRE_IN_SWEEP=1; in a geometric pass the sweep keeps its fit plane's and
+        // refinement candidates' geometric terms there once P2a has read the costs, unless
+        // APD_NO_GEOM_TAIL=1: the next iteration's candidate kernels, later on this stream, rewrite
+        // every entry P2a reads; otherwise they are read-only too). APD_WEAK_PER_COLOUR=1 keeps the launch per colour over the per-colour lists.
         if (!ctx->weak_per_colour && nw > 0 && ctx->wlist.bytes < (size_t)nw * sizeof(int)) {
             ctx->err = "WEAK lists not built by apd_stage_prepare";
             return APD_ESTATE;
@@ -5601,7 +5698,7 @@ int32_t apd_stage_iteration(apd_ctx *ctx, int32_t iter) {
                           (ctx->args.tex_f16 ? (ctx->args.sa_any ? wv_lds_bytes<true, 9, true>(a.N, direct) : wv_lds_bytes<true, 9, false>(a.N, direct))
                                              : (ctx->args.sa_any ? wv_lds_bytes<false, 9, true>(a.N, direct) : wv_lds_bytes<false, 9, false>(a.N, direct))),
                           s,
-                          aw, wl, n, iter, cand, wc, gm, (direct && !centre_kernel) ? 1 : 0);
+                          aw, wl, n, iter, cand, wc, gm, (direct && !centre_kernel) ? 1 : 0, ctx->geom_tail ? 1 : 0);
             prof_end(ctx, e0, APD_PROF_WEAK_SWEEP, n);
         }
         prof_end(ctx, ewp, APD_PROF_WEAK_PATH, ctx->cnt[2] + ctx->cnt[3]);

@@ -246,7 +246,10 @@ int32_t apd_profile_query(apd_ctx *ctx, double *sweep_ms_total, int64_t *sweep_l
        them: the image-wide pair table, RandomInitialization's kept costs, or the
        sweep itself), plus the fit-plane and refinement-candidate evaluations of views with weight
        > 0 the sweep actually issued (those its exact early exit proves unnecessary are not counted);
-   [2] geometric-consistency terms of the same evaluations (APD.cu:1561, 1583, 1037, 1079);
+   [2] geometric-consistency terms of the same evaluations (APD.cu:1561, 1583, 1037, 1079); with the
+       early exit's geometric tail (geometric passes, default) the fit plane's and the refinement
+       candidates' terms are those of all views with weight > 0, counted once where the sweep's
+       pre-passes compute them, not again at the evaluations that read them;
    [3] NCC-Old evaluations DepthToWeak issued (APD.cu:2155-2186: active pixel x disparity in range x
        selected view; disparities 0 and 60 only with the curve export);
    [4] geometric-consistency terms DepthToWeak issued;

@@ -25,13 +25,16 @@ c = list(c)[32:]  # the instrumented builds' slots (APD_INSTR = 32)
 names = {8: "cand setup (hash, windows)", 9: "cand pair windows", 10: "cand centre windows", 11: "cand focal combination",
          0: "sweep P0 anchors/windows", 1: "sweep P1 current plane", 2: "sweep P2 view selection+geom",
          3: "sweep P3 fit plane", 4: "sweep P4 candidates", 5: "sweep P5 refinement", 6: "sweep P6 acceptance"}
-for lo, hi, title in ((8, 12, "k_weak_cand_vm"), (0, 7, "k_sweep_weak_vm")):
-    tot = (sum(c[8 + i] for i in range(lo, hi)) + (c[30] + c[31] if lo == 0 else 0)) or 1
+for lo, hi, title in ((0, 7, "k_sweep_weak_vm"),):
+    # (the sweep's total: its stamps 0..6, P2a and P1-prime, and the geometric pre-passes at stamps 10, 11)
+    tot = (sum(c[8 + i] for i in range(lo, hi)) + (c[30] + c[31] + c[18] + c[19] if lo == 0 else 0)) or 1
     print(title)
     for i in range(lo, hi):
         print(f"  {names[i]:32s} {100.0 * c[8 + i] / tot:6.1f} %")
     if lo == 0:
         print(f"  {'sweep P1-prime cand centre windows':32s} {100.0 * c[31] / tot:6.1f} %   (P1 above is 0 when stamped)")
+        print(f"  {'sweep P3-prime fit geom terms + tail':32s} {100.0 * c[18] / tot:6.1f} %   (0 without the geometric tail)")
+        print(f"  {'sweep P5-prime cand geom terms + tail':32s} {100.0 * c[19] / tot:6.1f} %")
         print(f"  {'sweep P2a (before P1b)':32s} {100.0 * c[30] / tot:6.1f} %   (P2 above = P1b + P1c when stamped)")
         print(f"  (of P2a: geometric terms, thread 0's own time {100.0 * c[15] / max(c[30] or c[10], 1):5.1f} %)")
 t = eng.timing()
