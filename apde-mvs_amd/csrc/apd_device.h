@@ -932,9 +932,6 @@ __device__ __forceinline__ float ncc_old_fast_h(const Args &a, int px, int py, i
             else slow = true;
         }
     }
-#ifdef APD_ABLATE_NCC  // timing-only build: skeleton without the window sums
-    return fabsf(Hm.h[0] + Hm.h[8]) * 0.001f;
-#endif
     if (!window_rcp_ok(Hm, (float)(px - 5), (float)(py - 5)) || a.force_slow) slow = true;
     if (slow) {
 #pragma unroll

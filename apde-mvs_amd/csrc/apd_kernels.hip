@@ -65,9 +65,24 @@ using namespace apd;
 #define PHASE_BEGIN do { } while (0)
 #define LANE_STAT(slot, pred) do { } while (0)
 #endif
-#ifndef APD_SWEEP_WAVES
-#define APD_SWEEP_WAVES 2  // min waves per SIMD requested for the sweep kernels (VGPR budget 512/w)
-#endif
+// the public counters' slots of a.evals (apd_profile_counters, apd_hip.h)
+enum EvalSlot {
+    EV_STRONG_NCC = 0, EV_WEAK_NCC = 1, EV_WEAK_GEOM = 2, EV_DW_NCC = 3, EV_DW_GEOM = 4, EV_PAIR_WIN = 5,
+    EV_CAND_CENTRE_WIN = 6, EV_SWEEP_CENTRE_WIN = 7, EV_SWEEP_ANCHOR_WIN = 8
+};
+// k_sweep_weak_vm's PHASE_STAMP ids (tools/phase_profile.py reads them by number): the phase that ends
+// at the stamp
+enum WvStamp {
+    PS_P0 = 0, PS_P1 = 1, PS_P2 = 2, PS_P3 = 3, PS_P4 = 4, PS_P5 = 5, PS_P6 = 6,
+    PS_P2A_GEOM = 7,     // thread 0's own time in P2a's geometric terms (not barrier to barrier)
+    PS_P3_PRE = 10, PS_P5_PRE = 11,  // the geometric pre-passes P3' / P5'
+    PS_P2A = 22, PS_P1_PRIME = 23
+};
+// its LANE_STAT slots (pairs: waves, active lanes)
+enum WvLaneStat {
+    LS_P0_PIXELS = 0, LS_P0_CUR_IS_CAND = 2, LS_P0_FIT_IS_CUR = 4, LS_P0_FIT_IS_CAND = 6, LS_P1C_TAKEN = 16,
+    LS_P5_TASKS = 20, LS_P3_TASKS = 22, LS_P1B_TASKS = 24
+};
 
 // ---------------------------------------------------------------------------------------------
 // view-group lane mapping
@@ -238,31 +253,6 @@ __global__ __launch_bounds__(1024) void k_list_scan(const int *__restrict__ row_
     int off = part[threadIdx.x] - s;
     for (int r = r0; r < min(r0 + per, H); ++r) { row_off[r] = off; off += row_counts[r]; }
     if (threadIdx.x == 1023) *total = part[1023];
-}
-__global__ __launch_bounds__(BLOCK) void k_list_fill(Args a, int mode, int colour, const int *__restrict__ row_off,
-                                                   int *__restrict__ out) {
-    const int y = blockIdx.x;
-    __shared__ int wcnt[BLOCK / WAVE];
-    int off = row_off[y];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    for (int x0 = 0; x0 < a.W; x0 += BLOCK) {
-        const int x = x0 + threadIdx.x;
-        const bool p = x < a.W && list_pred(a, mode, colour, x, y);
-        const unsigned long long m = __ballot(p);
-        const int pre = __popcll(m & ((1ull << lane) - 1ull));
-        if (lane == 0) wcnt[wv] = __popcll(m);
-        __syncthreads();
-        int wo = 0;
-        for (int k = 0; k < wv; ++k) wo += wcnt[k];
-        const int tot = wcnt[0] + wcnt[1] + wcnt[2] + wcnt[3];
-        if (mode == 2) {
-            if (x < a.W) out[y * a.W + x] = p ? off + wo + pre : -1;
-        } else if (p) {
-            out[off + wo + pre] = y * a.W + x;
-        }
-        off += tot;
-        __syncthreads();
-    }
 }
 
 // Tile-ordered compaction for the sweep pixel sets (modes 0/1). The order of a sweep list does not
@@ -503,15 +493,10 @@ __device__ __forceinline__ bool anc_inlier(const Args &a, float d, float depth_d
 // < 2e-6 for unit (dx, dy) (each product <= 1 in magnitude, a few roundings of 2^-24 relative each), so
 // outside a 1e-4 band around thr (50x that bound) it has the same verdict; inside the band (or for a
 // NaN) the IEEE statement decides. Saves the IEEE sqrt and division on the search's dependent chain.
-#ifndef GA_ANGLE_FILTER
-#define GA_ANGLE_FILTER 1
-#endif
 __device__ __forceinline__ bool ga_angle_ok(float tdx, float tdy, float dx, float dy, float thr) {
-    if (GA_ANGLE_FILTER) {
-        const float r = __builtin_amdgcn_rsqf(tdx * tdx + tdy * tdy);
-        const float va = (tdx * r) * dx + (tdy * r) * dy;
-        if (fabsf(va - thr) > 1e-4f) return va > thr;
-    }
+    const float r = __builtin_amdgcn_rsqf(tdx * tdx + tdy * tdy);
+    const float va = (tdx * r) * dx + (tdy * r) * dy;
+    if (fabsf(va - thr) > 1e-4f) return va > thr;
     normalize2(tdx, tdy);
     return tdx * dx + tdy * dy > thr;
 }
@@ -533,13 +518,6 @@ struct FastMod {
 // points' depths gathered here instead -- one dependent load per found point in this latency-bound
 // search -- made it 24 -> 30 ms at C3; the fit kernel's wave gathers them in one round trip.)
 #define GA_STAGE_W 34
-#ifndef GA_PHILOX_LDS
-#define GA_PHILOX_LDS 1  // k_gen_anchors_fit: one Philox block per lane, shared through LDS
-#endif
-#ifndef GA_SEARCH_AHEAD
-#define GA_SEARCH_AHEAD 0  // the shift-1 search issues the next radius's lookup before judging this one
-                           // (measured slower at C3: anchors 57.1 -> 61.7 ms, profiles/r6_ab_gen_anchors.txt)
-#endif
 template <bool SPLIT>
 __global__ __launch_bounds__(BLOCK) void k_gen_anchors(Args a, uint32_t *__restrict__ stage, int wc) {
     const int c = blockIdx.x * BLOCK + threadIdx.x;
@@ -591,11 +569,10 @@ __global__ __launch_bounds__(BLOCK) void k_gen_anchors(Args a, uint32_t *__restr
                     normalize2(ddx, ddy);
                     // (measured: lookups of four radii issued together, judged in order, made this
                     // kernel slower at C3, 24.4 -> 32.1 ms: more registers, fewer waves in flight.)
-                    // One radius ahead: the next radius's lookup is issued before this one is judged,
-                    // so the gather's latency overlaps the verdict's arithmetic. A radius is live when
-                    // it is <= APD_MAX_SEARCH_RADIUS and its ray point is inside the image (else the
-                    // search ends there, drawing nothing); its lookup only when the probe is inside
-                    // the margin -- the same statements as one radius at a time.
+                    // (Likewise one radius ahead, 57.1 -> 61.7 ms: profiles/r6_ab_gen_anchors.txt.)
+                    // A radius is live when it is <= APD_MAX_SEARCH_RADIUS and its ray point is inside
+                    // the image (else the search ends there, drawing nothing); its lookup only when
+                    // the probe is inside the margin.
                     auto probe = [&](int radius, bool &live, short2 &nn) {
                         const float tx = (float)px + dx * (float)radius, ty = (float)py + dy * (float)radius;
                         live = radius <= APD_MAX_SEARCH_RADIUS && !(tx < 0 || ty < 0 || tx >= (float)W || ty >= (float)H);
@@ -604,23 +581,6 @@ __global__ __launch_bounds__(BLOCK) void k_gen_anchors(Args a, uint32_t *__restr
                         const bool in = live && !(ax < margin || ay < margin || ax >= W - margin || ay >= H - margin);
                         nn = in ? a.nearest[ax + ay * W] : make_short2(-1, -1);
                     };
-#if GA_SEARCH_AHEAD
-                    int radius = 2;
-                    bool live;
-                    short2 nn;
-                    probe(radius, live, nn);
-                    while (live) {
-                        const int rn = min(radius * 2, radius + 25);
-                        bool live_n;
-                        short2 nn_n;
-                        probe(rn, live_n, nn_n);
-                        bool ok = !(nn.x == -1 || nn.y == -1);
-                        if (ok) ok = ga_angle_ok((float)(nn.x - px), (float)(nn.y - py), dx, dy, a.anc_thr);
-                        g.n += ok ? 4u : 16u;
-                        if (ok) { found(di, nn); break; }
-                        radius = rn; live = live_n; nn = nn_n;
-                    }
-#else
                     for (int radius = 2; radius <= APD_MAX_SEARCH_RADIUS; radius = min(radius * 2, radius + 25)) {
                         bool live;
                         short2 nn;
@@ -631,7 +591,6 @@ __global__ __launch_bounds__(BLOCK) void k_gen_anchors(Args a, uint32_t *__restr
                         g.n += ok ? 4u : 16u;
                         if (ok) { found(di, nn); break; }
                     }
-#endif
                 } else
                 for (int radius = 2; radius <= APD_MAX_SEARCH_RADIUS; radius = min(radius * 2, radius + 25)) {
                     float tx = (float)px + dx * (float)radius, ty = (float)py + dy * (float)radius;
@@ -810,7 +769,6 @@ __global__ __launch_bounds__(GA_FIT_WAVES * WAVE, GA_FIT_MINW) void k_gen_anchor
     const Rng g(a.seed_lo, a.seed_hi, (uint32_t)c, ORD_ANCHORS);
     const FastMod fm((uint32_t)vc);
     const uint32_t d0 = (hdr >> 6) + 3u * (uint32_t)lane;
-#if GA_PHILOX_LDS
     // the 50 iterations' 150 draws lie in Philox blocks n / 4 .. n / 4 + 38: lane j generates block
     // n / 4 + j once into LDS and every lane reads its three words there (instead of two blocks per lane)
     __shared__ uint4 sphil[GA_FIT_WAVES][WAVE];
@@ -819,15 +777,6 @@ __global__ __launch_bounds__(GA_FIT_WAVES * WAVE, GA_FIT_MINW) void k_gen_anchor
     __builtin_amdgcn_wave_barrier();  // (LDS operations of one wave complete in order)
     const uint32_t *sw = reinterpret_cast<const uint32_t *>(&sphil[threadIdx.x >> 6][0]);
     auto pick = [&](uint32_t d) { return sw[d - 4u * nb]; };  // (d - 4 nb <= 3 + 3 * 63 + 2 < 256)
-#else
-    // the three draws d0 .. d0 + 2 lie in Philox blocks d0 / 4 and (d0 + 2) / 4: two blocks, not three
-    const uint4 b0 = g.block(d0 >> 2), b1 = g.block((d0 + 2u) >> 2);
-    auto pick = [&](uint32_t d) {
-        const uint4 b = (d >> 2) == (d0 >> 2) ? b0 : b1;
-        const uint32_t j = d & 3u;
-        return j == 0 ? b.x : (j == 1 ? b.y : (j == 2 ? b.z : b.w));
-    };
-#endif
     const int ia = (int)fm.mod(pick(d0));
     const int ib = (int)fm.mod(pick(d0 + 1u));
     const int ic = (int)fm.mod(pick(d0 + 2u));
@@ -1052,38 +1001,6 @@ __device__ __forceinline__ int view_selection(const float ca[8], float prior, in
     return w;
 }
 
-// The same with the pixel's 15 draws precomputed (u[k * us] = the k-th uniform() of its stream).
-__device__ __forceinline__ int view_selection_u(const float ca[8], float prior, int iter, const float *u, int us,
-                                                const Group &G, int N) {
-    const float thr = (float)(0.8 * (double)d_expf((float)(iter * iter) / (-90.0f)));
-    float count = 0.0f, tmpw = 0.0f;
-    int cf = 0;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const float c = ca[j];
-        if (c < thr) { tmpw += d_expf(c * c / (-0.18f)); count += 1.0f; }
-        if (c > 1.2f) cf++;
-    }
-    float sp = 0.0f;
-    if (count > 2 && cf < 3) sp = tmpw / count;
-    else if (cf < 3) sp = d_expf(thr * thr / (-0.32f));
-    sp = sp * prior;
-    float sum = 0.0f;
-    for (int k = 0; k < N; ++k) sum += __shfl(sp, G.base + k);
-    const float inv = 1.0f / sum;
-    float cum = 0.0f, mycdf = 0.0f;
-    for (int k = 0; k < N; ++k) {
-        cum = fmaf(__shfl(sp, G.base + k), inv, cum);
-        if (k == G.v) mycdf = cum;
-    }
-    int w = 0;
-    for (int smp = 0; smp < 15; ++smp) {
-        const float uu = u[smp * us] - APD_FLT_EPSILON;
-        const uint32_t m = group_bits(mycdf > uu, G);
-        if (m != 0u && (__ffs(m) - 1) == G.v) w++;
-    }
-    return w;
-}
 #define VS_DRAWS 15  // uniform() draws of view_selection
 
 // PlaneHypothesisRefinement{Strong,Weak} candidate generation (APD.cu:961-980 / 1054-1067)
@@ -1095,9 +1012,6 @@ __device__ __forceinline__ Cands refine_candidates(const Args &a, int px, int py
     const APD_C Cam &cam = a.cams[0];
     Cands C;
     C.drand = g.uniform() * (a.dmax - a.dmin) + a.dmin;
-#ifdef APD_ABLATE_RANDDEPTH  // timing-only experiment (wrong values): random-depth candidates kept local
-    C.drand = depth * 1.001f;
-#endif
     C.nrand = random_normal(cam, px, py, g, depth);
     float dp = depth;
     const float dminp = (1 - 0.02f) * dp;
@@ -1145,43 +1059,32 @@ __device__ __forceinline__ float4 candidate(const Cands &C, int k, float4 cur0, 
 // CU's 32 KiB L1 (contiguous per-wave chunks put up to 4 images per workgroup in flight; measured
 // on the Strong sweep: 13.5 -> 8.0 L1->L2 requests per gather, 16.2 -> 13.8 ms per launch).
 #define VM_P 64
-#ifndef APD_VM_LDS_PAD
-#define APD_VM_LDS_PAD 0  // experiments: extra LDS bytes per workgroup (fewer workgroups per CU)
-#endif
-// SS_LDS40 (fp16 problems): the reference taps as fp16 (exact there), the neighbour flags as bits and
-// the view selection's draws regenerated per (pixel, view) lane instead of kept in LDS -- 40.8 KB at
-// N = 10 (48.4 before): four workgroups per CU instead of three (the VGPRs bounded to match).
-#ifndef SS_LDS40
-#define SS_LDS40 1
-#endif
+// fp16 problems: the reference taps as fp16 (exact there), the neighbour flags as bits and the view
+// selection's draws regenerated per (pixel, view) lane instead of kept in LDS -- 40.8 KB at N = 10
+// (48.4 before): four workgroups per CU instead of three (the VGPRs bounded to match).
+// rows of the sweeps' per-pixel state st[row * VM_P + p]
+enum StRow {
+    ST_DEPTH_NOW = 0, ST_COST_NOW = 1,
+    ST_COST_INIT = 2,  // (Weak sweep: P2a's argmin cost until P1c)
+    ST_WNORM = 3       // weight norm
+};
 template <class RT>
 struct VmLdsT {  // static part; the cost table [9][N][64] and the weights [N][64] (uint8) follow
     RT refw[36 * VM_P];          // [k][p]
     float4 hyp[9 * VM_P];        // [h][p]: 8 propagated + current; P2 overwrites [0..4] with the
                                  // refinement candidates (VM_CAND) once the pixel's reads are done
-#if SS_LDS40
     uint8_t nvq[4 * VM_P];       // [w][p]: bit r = neighbour d = w + 4r exists (P0's wave w writes its own byte)
-#else
-    uint8_t nval[8 * VM_P];      // [d][p]: neighbour d exists (adaptive-checkerboard scan hit)
-#endif
     float4 pnow[VM_P];
-    float st[4 * VM_P];          // depth_now, cost_now, cost_init, weight_norm
-#if !SS_LDS40
-    float vsu[VS_DRAWS * VM_P];  // [k][p]: the view selection's 15 uniform() draws of the pixel's stream
-#endif
+    float st[4 * VM_P];          // [StRow][p]
     uint32_t tsel[VM_P];         // views with a sampled weight > 0
     float rmean[VM_P], rvar[VM_P];  // reference-window moments (RefWin) of pixel slot p (P3's packed items)
     int pxy[VM_P];               // packed (x, y) of pixel slot p
 };
 template <bool F16>
-using VmRefT = typename std::conditional<SS_LDS40 && F16, _Float16, float>::type;
+using VmRefT = typename std::conditional<F16, _Float16, float>::type;
 template <class RT>
 __device__ __forceinline__ bool vm_nval(const VmLdsT<RT> &L, int d, int p) {
-#if SS_LDS40
     return (L.nvq[(d & 3) * VM_P + p] >> (d >> 2)) & 1u;
-#else
-    return L.nval[d * VM_P + p] != 0;
-#endif
 }
 #ifndef SS_P3_CHUNKS
 #define SS_P3_CHUNKS 3  // Strong sweep P3 batches: whole views until at least this many 64-item chunks
@@ -1190,9 +1093,9 @@ __device__ __forceinline__ bool vm_nval(const VmLdsT<RT> &L, int d, int p) {
 // per-pixel SaWin table appended to the view-major kernels' dynamic LDS when the problem has SA masks
 static inline size_t sa_lds_bytes(const Args &a) { return a.sa_any ? VM_P * sizeof(SaWin) + 16 : 0; }
 __device__ __forceinline__ void *sa_lds_align(void *p) { return (void *)(((uintptr_t)p + 15) & ~(uintptr_t)15); }     // [k][p], k < 5: refinement candidates (t.w = distance)
-static inline size_t vm_lds_bytes(int N, bool f16) {
-    return APD_VM_LDS_PAD + (f16 ? sizeof(VmLdsT<VmRefT<true>>) : sizeof(VmLdsT<VmRefT<false>>)) +
-           (size_t)9 * N * VM_P * sizeof(float) + (size_t)N * VM_P;
+template <bool F16>
+static inline size_t vm_lds_bytes(int N) {
+    return sizeof(VmLdsT<VmRefT<F16>>) + (size_t)9 * N * VM_P * sizeof(float) + (size_t)N * VM_P;
 }
 
 // One direction of the adaptive checkerboard (APD.cu:1127-1316): d = 2*dir + far, dir in
@@ -1299,7 +1202,7 @@ template <bool F16, bool SA>
 #ifndef VM_MINW
 #define VM_MINW 3  // waves per SIMD -> VGPR budget 512 / VM_MINW
 #endif
-__global__ __launch_bounds__(VM_BLOCK, (SS_LDS40 && F16 && !SA) ? 4 : VM_MINW) void k_sweep_strong_vm(Args a, const int *__restrict__ list, int count,
+__global__ __launch_bounds__(VM_BLOCK, (F16 && !SA) ? 4 : VM_MINW) void k_sweep_strong_vm(Args a, const int *__restrict__ list, int count,
                                                                   int iter) {
     const int N = a.N, W = a.W, H = a.H;
     using VmLds = VmLdsT<VmRefT<F16>>;
@@ -1339,25 +1242,13 @@ __global__ __launch_bounds__(VM_BLOCK, (SS_LDS40 && F16 && !SA) ? 4 : VM_MINW) v
 #pragma unroll
             for (int r = 0; r < 2; ++r) {
                 const int d = wave + 4 * r;
-#if !SS_LDS40
-                L.nval[d * VM_P + p] = q[r] >= 0;
-#endif
                 if (q[r] >= 0) L.hyp[d * VM_P + p] = hp[r];
             }
-#if SS_LDS40
             L.nvq[wave * VM_P + p] = (uint8_t)((q[0] >= 0 ? 1u : 0u) | (q[1] >= 0 ? 2u : 0u));
-#endif
             if (wave == 0) { L.hyp[8 * VM_P + p] = hp[2]; L.pxy[p] = px | (py << 16); }
 #pragma unroll
             for (int kk = 0; kk < 36 / VM_WAVES; ++kk) L.refw[(wave + VM_WAVES * kk) * VM_P + p] = (VmRefT<F16>)rv[kk];
             if (SA && wave == VM_WAVES - 1) saw[p] = sa_window(a, px, py);
-#if !SS_LDS40
-            if (wave == 1 % VM_WAVES) {  // the view selection's draws, once per pixel (not per view lane)
-                Rng rg(a.seed_lo, a.seed_hi, (uint32_t)c, ord_strong(iter));
-#pragma unroll
-                for (int k = 0; k < VS_DRAWS; ++k) L.vsu[k * VM_P + p] = rg.uniform();
-            }
-#endif
         }
     }
     __syncthreads();
@@ -1436,12 +1327,8 @@ __global__ __launch_bounds__(VM_BLOCK, (SS_LDS40 && F16 && !SA) ? 4 : VM_MINW) v
             for (int i = 0; i < 4; ++i)
                 if (vm_nval(L, 2 * i, p)) prior += ((a.sel[nb[i]] >> v) & 1u) ? 0.9f : 0.1f;
         }
-#if SS_LDS40
         Rng rg(a.seed_lo, a.seed_hi, (uint32_t)c, ord_strong(iter));  // (the pixel's 15 draws, per lane)
         const int w = view_selection(ca, prior, iter, rg, G, N);
-#else
-        const int w = view_selection_u(ca, prior, iter, &L.vsu[p], VM_P, G, N);
-#endif
         const uint32_t tsel = group_bits(w > 0, G);
         if (G.valid) {
             wts[v * VM_P + p] = (uint8_t)w;
@@ -1506,10 +1393,10 @@ __global__ __launch_bounds__(VM_BLOCK, (SS_LDS40 && F16 && !SA) ? 4 : VM_MINW) v
             VM_CAND(L)[k * VM_P + p] = t;
         }
         L.pnow[p] = pnow;
-        L.st[0 * VM_P + p] = depth_now;
-        L.st[1 * VM_P + p] = cost_now;
-        L.st[2 * VM_P + p] = cost_init;
-        L.st[3 * VM_P + p] = wn;
+        L.st[ST_DEPTH_NOW * VM_P + p] = depth_now;
+        L.st[ST_COST_NOW * VM_P + p] = cost_now;
+        L.st[ST_COST_INIT * VM_P + p] = cost_init;
+        L.st[ST_WNORM * VM_P + p] = wn;
     }
     __syncthreads();
 
@@ -1634,7 +1521,7 @@ __global__ __launch_bounds__(VM_BLOCK, (SS_LDS40 && F16 && !SA) ? 4 : VM_MINW) v
                 }
                 nxt[i] = (uint8_t)v;
                 part[i] = P;
-                if (P / L.st[3 * VM_P + p] >= L.st[1 * VM_P + p]) dead[i] = 1;
+                if (P / L.st[ST_WNORM * VM_P + p] >= L.st[ST_COST_NOW * VM_P + p]) dead[i] = 1;
             }
             __syncthreads();
             v0 = v1;
@@ -1645,7 +1532,7 @@ __global__ __launch_bounds__(VM_BLOCK, (SS_LDS40 && F16 && !SA) ? 4 : VM_MINW) v
         uint32_t sum = issued;
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
-        if (lane == 0) atomicAdd(PROF_AT(a.evals, 0), (unsigned long long)sum);
+        if (lane == 0) atomicAdd(PROF_AT(a.evals, EV_STRONG_NCC), (unsigned long long)sum);
     }
 
     // ---- P4: weighted candidate costs in view order, acceptance, writes
@@ -1653,8 +1540,8 @@ __global__ __launch_bounds__(VM_BLOCK, (SS_LDS40 && F16 && !SA) ? 4 : VM_MINW) v
         const int p = p1, c = c1;
         for (int v = wave; v < N; v += VM_WAVES) a.vw[(size_t)v * a.HW + c] = (uint8_t)wts[v * VM_P + p];
         if (wave == 0) {
-            float cost_now = L.st[1 * VM_P + p];
-            const float cost_init = L.st[2 * VM_P + p], wn = L.st[3 * VM_P + p];
+            float cost_now = L.st[ST_COST_NOW * VM_P + p];
+            const float cost_init = L.st[ST_COST_INIT * VM_P + p], wn = L.st[ST_WNORM * VM_P + p];
             float4 pnow = L.pnow[p];
 #pragma unroll 1
             for (int k = 0; k < 5; ++k) {
@@ -1702,6 +1589,33 @@ __global__ __launch_bounds__(VM_BLOCK, (SS_LDS40 && F16 && !SA) ? 4 : VM_MINW) v
 // evaluations per pixel while this layout builds each window once per pixel; it was retired in round 5.)
 // SA = false (no SA masks in the problem): every tap of a window is valid, so the tap masks are
 // compile-time constants and their arrays shrink to one element.
+//
+// WvRefT::flags, one word per pixel slot (bit position, width):
+constexpr int WVF_HYP = 0, WVF_HYP_W = 8;    // bit h: anchor hypothesis h present (anchor h + 1 is STRONG)
+constexpr int WVF_CUR = 12, WVF_CUR_W = 3;   // the anchor hypothesis whose plane the current plane equals,
+constexpr int WVF_CUR_ON = 15;               // valid when this bit is set (WV_CUR_MATCH)
+constexpr int WVF_WIN = 16, WVF_WIN_W = 9;   // bit k: window k evaluated (anchor present, SA label matches)
+constexpr int WVF_BEST = 25, WVF_BEST_W = 3; // the best anchor hypothesis (Weak sweep P2a)
+constexpr int WVF_SA = 29;                   // the pixel has an SA label (its anchor windows are filtered)
+constexpr int WVF_REFINE = 31;               // refine (fit normal != 0)
+__device__ __forceinline__ uint32_t wvf_field(uint32_t f, int pos, int width) { return (f >> pos) & ((1u << width) - 1u); }
+__device__ __forceinline__ uint32_t wvf_hyps(uint32_t f) { return wvf_field(f, WVF_HYP, WVF_HYP_W); }
+__device__ __forceinline__ bool wvf_has_hyp(uint32_t f, int h) { return (f >> (WVF_HYP + h)) & 1u; }
+__device__ __forceinline__ bool wvf_cur_on(uint32_t f) { return (f >> WVF_CUR_ON) & 1u; }
+__device__ __forceinline__ int wvf_cur(uint32_t f) { return (int)wvf_field(f, WVF_CUR, WVF_CUR_W); }
+__device__ __forceinline__ uint32_t wvf_wins(uint32_t f) { return wvf_field(f, WVF_WIN, WVF_WIN_W); }
+__device__ __forceinline__ bool wvf_has_win(uint32_t f, int k) { return (f >> (WVF_WIN + k)) & 1u; }
+__device__ __forceinline__ int wvf_best(uint32_t f) { return (int)wvf_field(f, WVF_BEST, WVF_BEST_W); }
+__device__ __forceinline__ bool wvf_refine(uint32_t f) { return (f >> WVF_REFINE) != 0u; }
+__device__ __forceinline__ uint32_t wvf_cur_bits(int h) { return (1u << WVF_CUR_ON) | ((uint32_t)h << WVF_CUR); }
+__device__ __forceinline__ uint32_t wvf_win_bits(uint32_t wins) { return wins << WVF_WIN; }
+__device__ __forceinline__ uint32_t wvf_sa_bit(bool sa) { return sa ? (1u << WVF_SA) : 0u; }
+__device__ __forceinline__ uint32_t wvf_set_best(uint32_t f, int h) {
+    return (f & ~(((1u << WVF_BEST_W) - 1u) << WVF_BEST)) | ((uint32_t)h << WVF_BEST);
+}
+__device__ __forceinline__ uint32_t wvf_set_refine(uint32_t f) { return f | (1u << WVF_REFINE); }
+// slots of the exact early exit's geometric terms (gt_at): the fit plane, then the refinement candidates
+enum GtSlot { GT_FIT = 0, GT_CAND0 = 1 };
 template <bool F16, int NWIN = 9, bool SA = true>
 struct WvRefT {
     static constexpr int MP = SA ? VM_P : 1;  // per-pixel extent of the SA-only arrays
@@ -1710,11 +1624,7 @@ struct WvRefT {
     // once per evaluation: sr / wsum, var_ref -- the same statements (1 / wsum: inv_lut)
     float wsrp[NWIN * VM_P], wvar[NWIN * VM_P];
     int anc[9 * VM_P];           // packed (x, y) of anchors 0..8, -1 = none
-    uint32_t flags[VM_P];        // bits 0-7: hypothesis h present (anchor STRONG); 12-15: the current plane is
-                                 // hypothesis (bits 12-14) when bit 15; 16-24: window k evaluated
-                                 // (anchor present and SA label matches); 25-27: the best anchor
-                                 // hypothesis (Weak sweep P2a); 29: the pixel has an SA label (its anchor
-                                 // windows are filtered); 31: refine (fit normal != 0)
+    uint32_t flags[VM_P];        // packed per-pixel state: the WVF_* fields below
     // [tap][p]: window 0 taps 0..35 (6x6, step 2), anchor k taps 36+9(k-1).. (3x3, step 5); fp16 when
     // the images are (exactly) fp16-representable, see apd_set_problem
     typename std::conditional<F16, _Float16, float>::type rref[(36 + 9 * (NWIN - 1)) * VM_P];
@@ -1738,7 +1648,7 @@ struct WvLdsT : WvRefT<F16, NWIN, SA> {
     float4 hyp[9 * VM_P];        // [h][p]: anchor planes 1..8 (if STRONG) + current; P4 overwrites [0..4]
                                  // with the refinement candidates (WV_CAND) after P2's last read
     float4 pnow[VM_P];
-    float st[4 * VM_P];          // depth_now, cost_now, cost_init, weight norm
+    float st[4 * VM_P];          // [StRow][p]
     uint32_t tsel[VM_P];         // views with weight > 0 (the selection the best anchor hypothesis brings)
     uint16_t rng_n[VM_P];
     int pxy[VM_P];               // packed (x, y) of pixel slot p (P5's packed items)
@@ -1757,12 +1667,9 @@ __host__ __device__ __forceinline__ int wv_cost_rows(int N, bool direct) {
     const int base = direct ? N : 9 * N;
     return base > p5 ? base : p5;
 }
-#ifndef APD_WV_LDS_PAD
-#define APD_WV_LDS_PAD 0  // experiments: extra LDS bytes per workgroup (fewer workgroups per CU)
-#endif
 template <bool F16, int NWIN, bool SA>
 static inline size_t wv_lds_bytes(int N, bool direct = false) {
-    return APD_WV_LDS_PAD + sizeof(WvLdsT<F16, NWIN, SA>) + (size_t)wv_cost_rows(N, direct) * VM_P * sizeof(float) +
+    return sizeof(WvLdsT<F16, NWIN, SA>) + (size_t)wv_cost_rows(N, direct) * VM_P * sizeof(float) +
            (size_t)2 * N * VM_P;
 }
 // Occupancy: the fp16 instantiations (direct) at N = 10 fit four workgroups per CU (160 KiB of LDS).
@@ -2117,7 +2024,7 @@ __device__ __forceinline__ float ncc_new_centre(const Args &a, const WvRefT<F16,
                                                 bool &dead, uint32_t *nwc) {
     const int W = a.W, H = a.H;
     const int pk = L.anc[p];
-    const bool has = alive && pk >= 0 && ((L.flags[p] >> 16) & 1u);
+    const bool has = alive && pk >= 0 && wvf_has_win(L.flags[p], 0);
     const int ax = has ? (pk & 0xFFFF) : px, ay = has ? (pk >> 16) : py;
     bool live = has;
     if (has) {
@@ -2177,7 +2084,7 @@ __device__ __forceinline__ float ncc_new_vm(const Args &a, const WvRefT<F16, NWI
     const bool box_ok = hd.box_ok;
     const TT T(a, s);
     const SrcTex<F16> Q(a, s);
-    const uint32_t awin = (L.flags[p] >> 16) & 0x1FFu;
+    const uint32_t awin = wvf_wins(L.flags[p]);
     float sc[9];
     int ns = 0;
     float strong_weight = 0.0f;
@@ -2187,12 +2094,7 @@ __device__ __forceinline__ float ncc_new_vm(const Args &a, const WvRefT<F16, NWI
     for (int k = 1; k < 9; ++k) {
         const int pk = L.anc[k * VM_P + p];
         const bool has = alive && pk >= 0 && ((awin >> k) & 1u);
-#ifdef APD_ABLATE_ANCHOR_LOCAL  // timing-only (wrong values): anchor windows k >= 1 next to the pixel
-        const int ax = has ? min(max(px + 6 * (((k - 1) % 3) - 1), 0), W - 1) : px;
-        const int ay = has ? min(max(py + 6 * (((k - 1) / 3) - 1), 0), H - 1) : py;
-#else
         const int ax = has ? (pk & 0xFFFF) : px, ay = has ? (pk >> 16) : py;
-#endif
         bool live = has;
         if (has) {
             float asx, asy;
@@ -2257,11 +2159,6 @@ __device__ __forceinline__ float ncc_new_vm(const Args &a, const WvRefT<F16, NWI
 #endif
 #ifndef WV_CUR_MATCH
 #define WV_CUR_MATCH 1  // P1b takes the current plane's costs from P2a when it is an anchor candidate's plane
-#endif
-#ifndef WV_P2_GEOM_BATCH
-// P2a's 8 geometric terms with their gathers batched (1) or one at a time (0): batched was -0.7 % at
-// three workgroups per CU, one at a time is -0.3 % at four (profiles/r5_ab_sa_occ4.txt, r5_ab_kept_lanes.txt)
-#define WV_P2_GEOM_BATCH 0
 #endif
 #define WV_BLOCK (WV_WAVES * WAVE)
 // The anchor candidates' costs (k_weak_cand_g writes the centre costs, k_weak_cand_comb combines in
@@ -2406,17 +2303,17 @@ __global__ __launch_bounds__(WV_BLOCK, (WvOcc<F16, SA>::occ)) void k_sweep_weak_
             }
             // the current plane bitwise equal to STRONG anchor k's (a pixel keeps the anchor hypothesis
             // it took while neither plane changes): its NCC-New and geometric terms are anchor candidate
-            // k - 1's, which P2a holds -- flags bit 15 + (k - 1) << 12, the first such k (WV_CUR_MATCH)
+            // k - 1's, which P2a holds -- wvf_cur_bits(k - 1), the first such k (WV_CUR_MATCH)
             uint32_t cmatch = 0;
 #pragma unroll
             for (int k = 8; k >= 1; --k)
                 if (WV_CUR_MATCH && ((hflag >> (k - 1)) & 1u) && __float_as_uint(hp[k].x) == __float_as_uint(cur.x) &&
                     __float_as_uint(hp[k].y) == __float_as_uint(cur.y) && __float_as_uint(hp[k].z) == __float_as_uint(cur.z) &&
                     __float_as_uint(hp[k].w) == __float_as_uint(cur.w))
-                    cmatch = (1u << 15) | ((uint32_t)(k - 1) << 12);
-            L.flags[p1] = hflag | cmatch | (awin << 16) | (use_sa ? (1u << 29) : 0u);
-            LANE_STAT(0, true);         // (instrumented builds: pixels, and those whose current plane
-            LANE_STAT(2, cmatch != 0);  //  is an anchor candidate's)
+                    cmatch = wvf_cur_bits(k - 1);
+            L.flags[p1] = hflag | cmatch | wvf_win_bits(awin) | wvf_sa_bit(use_sa);
+            LANE_STAT(LS_P0_PIXELS, true);  // (instrumented builds: pixels, and those whose current plane
+            LANE_STAT(LS_P0_CUR_IS_CAND, cmatch != 0);  // is an anchor candidate's)
 #ifdef APD_PHASE_STAMPS
             {  // (instrumented builds: the fit plane equal to the current plane / to an anchor candidate's)
                 const float4 ft = a.fit[c1];
@@ -2428,8 +2325,8 @@ __global__ __launch_bounds__(WV_BLOCK, (WvOcc<F16, SA>::occ)) void k_sweep_weak_
 #pragma unroll
                 for (int k = 1; k < 9; ++k) fc = fc || (((hflag >> (k - 1)) & 1u) && same(hp[k], ft));
                 const bool has_fit = !(ft.x == 0 && ft.y == 0 && ft.z == 0);
-                LANE_STAT(4, has_fit && same(ft, cur));
-                LANE_STAT(6, has_fit && fc);
+                LANE_STAT(LS_P0_FIT_IS_CUR, has_fit && same(ft, cur));
+                LANE_STAT(LS_P0_FIT_IS_CAND, has_fit && fc);
             }
 #endif
             L.hyp[8 * VM_P + p1] = cur;
@@ -2447,7 +2344,7 @@ __global__ __launch_bounds__(WV_BLOCK, (WvOcc<F16, SA>::occ)) void k_sweep_weak_
         wv_build_windows<F16>(a, L, p1, anc, cid, wave, WV_WAVES);
     }
     __syncthreads();
-    PHASE_STAMP(0);
+    PHASE_STAMP(PS_P0);
 
     // ---- P1 (not direct): (anchor hypothesis, view) tasks, lane = pixel. The current plane is
     // evaluated after the view selection (P1b), for the views it weights only: cost_now = sum of
@@ -2458,7 +2355,7 @@ __global__ __launch_bounds__(WV_BLOCK, (WvOcc<F16, SA>::occ)) void k_sweep_weak_
     for (int u = wave; u < ntask; u += WV_WAVES) {  // view-major: the waves share a source image
         const int v = u / 8, h = u - 8 * v, t = h * N + v;
         float val = (h == 0 && v == 0) ? 2.0f : 0.0f;
-        const bool want = pv1 && ((L.flags[p1] >> h) & 1u);
+        const bool want = pv1 && wvf_has_hyp(L.flags[p1], h);
         const float4 pl = L.hyp[h * VM_P + p1];
         const float nv = ncc_new_vm<F16, SA, true, 9, PIPE>(a, L, p1, px1, py1, v + 1, pl, want, nullptr, &nwc, &nwa);
         if (want) val = nv;
@@ -2474,7 +2371,7 @@ __global__ __launch_bounds__(WV_BLOCK, (WvOcc<F16, SA>::occ)) void k_sweep_weak_
         const int wi1 = gm ? 0 : a.amap[c1];
         for (int u = wave; u < 8 * N; u += WV_WAVES) {
             const int v = u / 8, h = u - 8 * v;
-            const bool want = pv1 && ((L.flags[p1] >> h) & 1u);
+            const bool want = pv1 && wvf_has_hyp(L.flags[p1], h);
             if (!__ballot(want)) continue;
             const float4 pl = L.hyp[h * VM_P + p1];
             bool dead;
@@ -2486,8 +2383,8 @@ __global__ __launch_bounds__(WV_BLOCK, (WvOcc<F16, SA>::occ)) void k_sweep_weak_
         }
     }
     __syncthreads();
-    if (direct && centre_in_sweep) PHASE_STAMP(23);  // (instrumented builds: P1' apart from P1)
-    else PHASE_STAMP(1);
+    if (direct && centre_in_sweep) PHASE_STAMP(PS_P1_PRIME);  // (instrumented builds: P1' apart from P1)
+    else PHASE_STAMP(PS_P1);
 
     // ---- P2a: lane = (pixel, view) groups: view selection, the anchor hypotheses' weighted costs
     // (with their geometric terms) and their argmin
@@ -2506,7 +2403,7 @@ __global__ __launch_bounds__(WV_BLOCK, (WvOcc<F16, SA>::occ)) void k_sweep_weak_
         const int p = min(pr, np - 1);
         const int c = list[first + p];
         const int py = c / W, px = c - py * W;
-        const uint32_t hflag = L.flags[p] & 0x1FFu;
+        const uint32_t hflag = L.flags[p] & ((1u << (WVF_HYP_W + 1)) - 1u);  // the WVF_HYP field (and the unused bit 8)
         float prior = 0.0f;
         const uint32_t asv = asl[v * VM_P + p];
 #pragma unroll
@@ -2532,28 +2429,6 @@ __global__ __launch_bounds__(WV_BLOCK, (WvOcc<F16, SA>::occ)) void k_sweep_weak_
 #ifdef APD_PHASE_STAMPS
         const long long tg0_ = clock64();
 #endif
-#if WV_P2_GEOM_BATCH
-        // the 8 geometric terms with their source-depth gathers all in flight before the first is
-        // consumed (geom_head / geom_tail: the same statements as geom_cost)
-        if (geom && w > 0) {
-            GeomHead gh[8];
-            float sdep[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                float P[3];
-                geom_point(a, px, py, L.hyp[j * VM_P + p], P);
-                gh[j] = geom_head(a, v + 1, P);
-            }
-#pragma unroll
-            for (int j = 0; j < 8; ++j) sdep[j] = ((hflag >> j) & 1u) ? a.depth[gh[j].idx] : 0.0f;
-#pragma unroll
-            for (int j = 0; j < 8; ++j)
-                gval[j] = ((hflag >> j) & 1u) ? fmaf(gf, geom_tail(a, px, py, v + 1, gh[j], sdep[j]), ca[j]) : fmaf(gf, 3.0f, ca[j]);
-        } else {
-#pragma unroll
-            for (int j = 0; j < 8; ++j) gval[j] = ca[j];
-        }
-#else
         // the candidates' world points (geom_point: depth_from_plane and world_point, view-independent)
         // once per (pixel, candidate) instead of once per (pixel, view, candidate): with N >= 8 view
         // lanes per pixel, lane v computes candidate v's and the group's lanes read it by shuffle --
@@ -2580,15 +2455,14 @@ __global__ __launch_bounds__(WV_BLOCK, (WvOcc<F16, SA>::occ)) void k_sweep_weak_
 #pragma unroll
             for (int k = 0; k < 8; ++k) if (j == k) gval[k] = vv;
         }
-#endif
 #ifdef APD_PHASE_STAMPS
-        if (a.evals && threadIdx.x == 0) atomicAdd(PROF_AT(a.evals, APD_INSTR + 8 + 7), (unsigned long long)(clock64() - tg0_));
+        if (a.evals && threadIdx.x == 0) atomicAdd(PROF_AT(a.evals, APD_INSTR + 8 + PS_P2A_GEOM), (unsigned long long)(clock64() - tg0_));
 #endif
         // the current plane is anchor candidate m's: P1b's cost for this view (its NCC-New + geometric
         // term, 0 for a view without weight) is gval[m], the same statements on the same inputs
         const uint32_t flp = L.flags[p];
-        if (WV_CUR_MATCH && ((flp >> 15) & 1u)) {
-            const int m = (int)((flp >> 12) & 7u);
+        if (WV_CUR_MATCH && wvf_cur_on(flp)) {
+            const int m = wvf_cur(flp);
             float gm = gval[0];
 #pragma unroll
             for (int k = 1; k < 8; ++k) if (m == k) gm = gval[k];
@@ -2616,11 +2490,11 @@ __global__ __launch_bounds__(WV_BLOCK, (WvOcc<F16, SA>::occ)) void k_sweep_weak_
             wts[v * VM_P + p] = (uint8_t)w;
             if (G.v == 0) {
                 const float4 fit = a.fit[c];
-                L.st[2 * VM_P + p] = fcm;  // (P1c: the argmin's weighted cost, then cost_init)
-                L.st[3 * VM_P + p] = wn;
+                L.st[ST_COST_INIT * VM_P + p] = fcm;  // (P1c: the argmin's weighted cost, then cost_init)
+                L.st[ST_WNORM * VM_P + p] = wn;
                 L.tsel[p] = tsel;
-                uint32_t fl = (L.flags[p] & ~(7u << 25)) | ((uint32_t)mi << 25);
-                if (!(fit.x == 0 && fit.y == 0 && fit.z == 0)) fl |= 1u << 31;
+                uint32_t fl = wvf_set_best(L.flags[p], mi);
+                if (!(fit.x == 0 && fit.y == 0 && fit.z == 0)) fl = wvf_set_refine(fl);
                 L.flags[p] = fl;
                 L.rng_n[p] = (uint16_t)rg.n;  // a few dozen draws
             }
@@ -2628,14 +2502,14 @@ __global__ __launch_bounds__(WV_BLOCK, (WvOcc<F16, SA>::occ)) void k_sweep_weak_
     }
     __syncthreads();
 
-    PHASE_STAMP(22);  // (instrumented builds: P2a apart from P1b + P1c)
+    PHASE_STAMP(PS_P2A);  // (instrumented builds: P2a apart from P1b + P1c)
     // ---- P1b: current-plane tasks, lane = pixel, for the views with weight > 0
     const int cur_row = direct ? 0 : 8 * N;
-    const bool cur_shared = WV_CUR_MATCH && pv1 && ((L.flags[p1] >> 15) & 1u);  // (P2a wrote its row)
+    const bool cur_shared = WV_CUR_MATCH && pv1 && wvf_cur_on(L.flags[p1]);  // (P2a wrote its row)
     for (int v = wave; v < N; v += WV_WAVES) {
         float val = 0.0f;
         const bool want = pv1 && wts[v * VM_P + p1] > 0 && !cur_shared;
-        LANE_STAT(24, want);
+        LANE_STAT(LS_P1B_TASKS, want);
         if (__ballot(want)) {
             const float4 pl = L.hyp[8 * VM_P + p1];
             // iteration 0: the current plane is RandomInitialization's, whose NCC-New it kept (a.wcur)
@@ -2658,7 +2532,7 @@ __global__ __launch_bounds__(WV_BLOCK, (WvOcc<F16, SA>::occ)) void k_sweep_weak_
 
     // ---- P1c: lane = pixel (wave 0): the current plane's cost, acceptance of the best anchor hypothesis
     if (wave == 0 && pv1) {
-        const float wn = L.st[3 * VM_P + p1];
+        const float wn = L.st[ST_WNORM * VM_P + p1];
         float cost_now = 0.0f;
         for (int k = 0; k < N; ++k) {
             const int wk = wts[k * VM_P + p1];
@@ -2666,13 +2540,13 @@ __global__ __launch_bounds__(WV_BLOCK, (WvOcc<F16, SA>::occ)) void k_sweep_weak_
         }
         cost_now /= wn;
         const float cost_init = cost_now;
-        const int mi = (int)((L.flags[p1] >> 25) & 7u);
-        const float fcm = L.st[2 * VM_P + p1];
+        const int mi = wvf_best(L.flags[p1]);
+        const float fcm = L.st[ST_COST_INIT * VM_P + p1];
         const float4 cur = L.hyp[8 * VM_P + p1];
         float depth_now = depth_from_plane(cam0, cur, px1, py1);
         float4 pnow = cur;
         bool taken = false;
-        if ((L.flags[p1] >> mi) & 1u) {
+        if (wvf_has_hyp(L.flags[p1], mi)) {
             const float4 cnd = L.hyp[mi * VM_P + p1];
             const float db = depth_from_plane(cam0, cnd, px1, py1);
             if (db >= a.dmin && db <= a.dmax && fcm < cost_now) {
@@ -2681,15 +2555,15 @@ __global__ __launch_bounds__(WV_BLOCK, (WvOcc<F16, SA>::occ)) void k_sweep_weak_
                 taken = true;
             }
         }
-        LANE_STAT(16, taken);  // (instrumented builds: pixels that take the best anchor hypothesis)
+        LANE_STAT(LS_P1C_TAKEN, taken);  // (instrumented builds: pixels that take the best anchor hypothesis)
         L.pnow[p1] = pnow;
-        L.st[0 * VM_P + p1] = depth_now;
-        L.st[1 * VM_P + p1] = cost_now;
-        L.st[2 * VM_P + p1] = cost_init;
+        L.st[ST_DEPTH_NOW * VM_P + p1] = depth_now;
+        L.st[ST_COST_NOW * VM_P + p1] = cost_now;
+        L.st[ST_COST_INIT * VM_P + p1] = cost_init;
     }
     __syncthreads();
-    PHASE_STAMP(2);
-    const bool refine = pv1 && (L.flags[p1] >> 31) != 0u;
+    PHASE_STAMP(PS_P2);
+    const bool refine = pv1 && wvf_refine(L.flags[p1]);
     const float4 fit1 = a.fit[c1];
     uint32_t issued_nn = 0, issued_g = 0;  // profiling: P3/P5 evaluations this lane issued
 
@@ -2750,8 +2624,8 @@ __global__ __launch_bounds__(WV_BLOCK, (WvOcc<F16, SA>::occ)) void k_sweep_weak_
             nxt[it] = (uint8_t)v;
             part[it] = P;
             float T = P;
-            if (gtail && p < np && (L.flags[p] >> 31)) T = tail(s, p, v, P);
-            if (T / L.st[3 * VM_P + p] >= L.st[1 * VM_P + p]) dead[it] = 1;
+            if (gtail && p < np && wvf_refine(L.flags[p])) T = tail(s, p, v, P);
+            if (T / L.st[ST_WNORM * VM_P + p] >= L.st[ST_COST_NOW * VM_P + p]) dead[it] = 1;
         }
     };
 
@@ -2760,14 +2634,14 @@ __global__ __launch_bounds__(WV_BLOCK, (WvOcc<F16, SA>::occ)) void k_sweep_weak_
     if (gtail) {
         for (int v = wave; v < N; v += WV_WAVES) {
             if (refine && wts[v * VM_P + p1] > 0) {
-                *gt_at(v, 0, p1) = geom_cost(a, px1, py1, v + 1, fit1);
+                *gt_at(v, GT_FIT, p1) = geom_cost(a, px1, py1, v + 1, fit1);
                 ++issued_g;
             }
         }
         __syncthreads();
         fold(0, 1, 0, 0, 0, true);
         __syncthreads();
-        PHASE_STAMP(10);  // (instrumented builds: the fit plane's pre-pass apart from P3)
+        PHASE_STAMP(PS_P3_PRE);  // (instrumented builds: the fit plane's pre-pass apart from P3)
     }
 
     // ---- P3: fit-plane tasks (views with weight > 0), early exit against the cost after P2
@@ -2780,12 +2654,12 @@ __global__ __launch_bounds__(WV_BLOCK, (WvOcc<F16, SA>::occ)) void k_sweep_weak_
         if (v < N) {
             float cv = 0.0f;
             const bool want = refine && wts[v * VM_P + p1] > 0 && !dead[p1];
-            LANE_STAT(22, want);
+            LANE_STAT(LS_P3_TASKS, want);
             const float4 fit = fit1;
             const float nv = ncc_new_vm<F16, SA, true, 9, PIPE>(a, L, p1, px1, py1, v + 1, fit, want, nullptr, &nwc, &nwa);
             if (want) {
                 cv = nv;
-                if (gtail) cv = fmaf(gf, *gt_at(v, 0, p1), cv);  // (P3' computed the term)
+                if (gtail) cv = fmaf(gf, *gt_at(v, GT_FIT, p1), cv);  // (P3' computed the term)
                 else if (geom) { cv = fmaf(gf, geom_cost(a, px1, py1, v + 1, fit), cv); ++issued_g; }
                 ++issued_nn;
             }
@@ -2793,12 +2667,12 @@ __global__ __launch_bounds__(WV_BLOCK, (WvOcc<F16, SA>::occ)) void k_sweep_weak_
         }
         __syncthreads();
     }
-    PHASE_STAMP(3);
+    PHASE_STAMP(PS_P3);
 
     // ---- P4: fit acceptance, refinement candidates (PlaneHypothesisRefinementWeak, APD.cu:1008-1067)
     if (wave == 0 && refine) {
-        const float wn = L.st[3 * VM_P + p1];
-        float depth_now = L.st[0 * VM_P + p1], cost_now = L.st[1 * VM_P + p1];
+        const float wn = L.st[ST_WNORM * VM_P + p1];
+        float depth_now = L.st[ST_DEPTH_NOW * VM_P + p1], cost_now = L.st[ST_COST_NOW * VM_P + p1];
         float4 pnow = L.pnow[p1];
         const float4 fit = fit1;
         if (!dead[p1]) {  // (dead: the fit plane's cost reaches cost_now -- rejected)
@@ -2822,11 +2696,11 @@ __global__ __launch_bounds__(WV_BLOCK, (WvOcc<F16, SA>::occ)) void k_sweep_weak_
             WV_CAND(L)[k * VM_P + p1] = t;
         }
         L.pnow[p1] = pnow;
-        L.st[0 * VM_P + p1] = depth_now;
-        L.st[1 * VM_P + p1] = cost_now;
+        L.st[ST_DEPTH_NOW * VM_P + p1] = depth_now;
+        L.st[ST_COST_NOW * VM_P + p1] = cost_now;
     }
     __syncthreads();
-    PHASE_STAMP(4);
+    PHASE_STAMP(PS_P4);
 
     // ---- P5: candidate evaluations (views with weight > 0), early exit against the cost after the fit
     // plane (slots 1..5). Per view the (candidate, pixel) items that are still wanted are packed into
@@ -2850,7 +2724,7 @@ __global__ __launch_bounds__(WV_BLOCK, (WvOcc<F16, SA>::occ)) void k_sweep_weak_
         auto fold5 = [&](int v0, int v1, uint64_t ne) {
             for (int i = tid; i < 5 * VM_P; i += WV_BLOCK) {
                 const int k = i / VM_P, p = i - k * VM_P, sl = (1 + k) * VM_P + p;
-                if (dead[sl] || !(p < np && (L.flags[p] >> 31))) continue;
+                if (dead[sl] || !(p < np && wvf_refine(L.flags[p]))) continue;
                 int v = nxt[sl];
                 float P = part[sl];
                 for (; v < v1; ++v) {
@@ -2860,7 +2734,7 @@ __global__ __launch_bounds__(WV_BLOCK, (WvOcc<F16, SA>::occ)) void k_sweep_weak_
                 nxt[sl] = (uint8_t)v;
                 part[sl] = P;
                 const float T = gtail ? tail(1 + k, p, v, P) : P;
-                if (T / L.st[3 * VM_P + p] >= L.st[1 * VM_P + p]) dead[sl] = 1;
+                if (T / L.st[ST_WNORM * VM_P + p] >= L.st[ST_COST_NOW * VM_P + p]) dead[sl] = 1;
             }
         };
         // ---- P5': the candidates' geometric terms (views with weight > 0), wave = view, lane = pixel,
@@ -2881,14 +2755,14 @@ __global__ __launch_bounds__(WV_BLOCK, (WvOcc<F16, SA>::occ)) void k_sweep_weak_
 #pragma unroll
                     for (int k = 0; k < 5; ++k) sdep[k] = a.depth[gh[k].idx];
 #pragma unroll
-                    for (int k = 0; k < 5; ++k) *gt_at(v, 1 + k, p1) = geom_tail(a, px1, py1, v + 1, gh[k], sdep[k]);
+                    for (int k = 0; k < 5; ++k) *gt_at(v, GT_CAND0 + k, p1) = geom_tail(a, px1, py1, v + 1, gh[k], sdep[k]);
                     issued_g += 5;
                 }
             }
             __syncthreads();
             fold5(0, 0, 0);
             __syncthreads();
-            PHASE_STAMP(11);  // (instrumented builds: the candidates' pre-pass apart from P5)
+            PHASE_STAMP(PS_P5_PRE);  // (instrumented builds: the candidates' pre-pass apart from P5)
         }
         for (int v0 = 0; v0 < N;) {
             int v1 = v0, nch = 0, nne = 0;
@@ -2929,11 +2803,11 @@ __global__ __launch_bounds__(WV_BLOCK, (WvOcc<F16, SA>::occ)) void k_sweep_weak_
                     const int pxy = L.pxy[p];
                     const int px = pxy & 0xFFFF, py = pxy >> 16;
                     const float4 tp = WV_CAND(L)[k * VM_P + p];
-                    LANE_STAT(20, want);
+                    LANE_STAT(LS_P5_TASKS, want);
                     const float nv = ncc_new_vm<F16, SA, true, 9, PIPE>(a, L, p, px, py, v + 1, tp, want, nullptr, &nwc, &nwa);
                     if (want) {
                         float cv = nv;
-                        if (gtail) cv = fmaf(gf, *gt_at(v, 1 + k, p), cv);  // (P5' computed the term)
+                        if (gtail) cv = fmaf(gf, *gt_at(v, GT_CAND0 + k, p), cv);  // (P5' computed the term)
                         else if (geom) { cv = fmaf(gf, geom_cost(a, px, py, v + 1, tp), cv); ++issued_g; }
                         ++issued_nn;
                         costL[(k * VB + __builtin_popcountll(ne & ((1ull << (v - v0)) - 1ull))) * VM_P + p] = cv;
@@ -2946,7 +2820,7 @@ __global__ __launch_bounds__(WV_BLOCK, (WvOcc<F16, SA>::occ)) void k_sweep_weak_
             v0 = v1;
         }
     }
-    PHASE_STAMP(5);
+    PHASE_STAMP(PS_P5);
 
     if (a.evals && wave == 0) {
         // profiling: the NCC-New evaluations and geometric terms CheckerboardPropagationWeak issues
@@ -2958,13 +2832,13 @@ __global__ __launch_bounds__(WV_BLOCK, (WvOcc<F16, SA>::occ)) void k_sweep_weak_
         if (pv1) {
             int nsel = 0;
             for (int v = 0; v < N; ++v) nsel += wts[v * VM_P + p1] > 0;
-            const int nh = __builtin_popcount(L.flags[p1] & 0xFFu);
+            const int nh = __builtin_popcount(wvf_hyps(L.flags[p1]));
             nn = (uint32_t)(nh * N + nsel);
             ng = geom ? (uint32_t)(nh * nsel + nsel) : 0u;
         }
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) { nn += __shfl_xor(nn, o); ng += __shfl_xor(ng, o); }
-        if (lane == 0) { atomicAdd(PROF_AT(a.evals, 1), (unsigned long long)nn); atomicAdd(PROF_AT(a.evals, 2), (unsigned long long)ng); }
+        if (lane == 0) { atomicAdd(PROF_AT(a.evals, EV_WEAK_NCC), (unsigned long long)nn); atomicAdd(PROF_AT(a.evals, EV_WEAK_GEOM), (unsigned long long)ng); }
     }
     if (a.evals) {  // ... plus the fit-plane and refinement evaluations every wave issued (P3, P5)
         uint32_t nn = issued_nn, ng = issued_g, wc0 = nwc, wa0 = nwa, wp0 = nwp;
@@ -2974,9 +2848,9 @@ __global__ __launch_bounds__(WV_BLOCK, (WvOcc<F16, SA>::occ)) void k_sweep_weak_
             wc0 += __shfl_xor(wc0, o); wa0 += __shfl_xor(wa0, o); wp0 += __shfl_xor(wp0, o);
         }
         if (lane == 0) {
-            atomicAdd(PROF_AT(a.evals, 1), (unsigned long long)nn); atomicAdd(PROF_AT(a.evals, 2), (unsigned long long)ng);
-            atomicAdd(PROF_AT(a.evals, 7), (unsigned long long)wc0); atomicAdd(PROF_AT(a.evals, 8), (unsigned long long)wa0);
-            if (wp0) atomicAdd(PROF_AT(a.evals, 6), (unsigned long long)wp0);  // (P1': the candidates' centre windows)
+            atomicAdd(PROF_AT(a.evals, EV_WEAK_NCC), (unsigned long long)nn); atomicAdd(PROF_AT(a.evals, EV_WEAK_GEOM), (unsigned long long)ng);
+            atomicAdd(PROF_AT(a.evals, EV_SWEEP_CENTRE_WIN), (unsigned long long)wc0); atomicAdd(PROF_AT(a.evals, EV_SWEEP_ANCHOR_WIN), (unsigned long long)wa0);
+            if (wp0) atomicAdd(PROF_AT(a.evals, EV_CAND_CENTRE_WIN), (unsigned long long)wp0);  // (P1': the candidates' centre windows)
         }
     }
 
@@ -2984,8 +2858,8 @@ __global__ __launch_bounds__(WV_BLOCK, (WvOcc<F16, SA>::occ)) void k_sweep_weak_
     if (pv1) {
         for (int v = wave; v < N; v += WV_WAVES) a.vw[(size_t)v * a.HW + c1] = (uint8_t)wts[v * VM_P + p1];
         if (wave == 0) {
-            float cost_now = L.st[1 * VM_P + p1];
-            const float cost_init = L.st[2 * VM_P + p1], wn = L.st[3 * VM_P + p1];
+            float cost_now = L.st[ST_COST_NOW * VM_P + p1];
+            const float cost_init = L.st[ST_COST_INIT * VM_P + p1], wn = L.st[ST_WNORM * VM_P + p1];
             float4 pnow = L.pnow[p1];
             if (refine) {
                 for (int k = 0; k < 5; ++k) {
@@ -3006,7 +2880,7 @@ __global__ __launch_bounds__(WV_BLOCK, (WvOcc<F16, SA>::occ)) void k_sweep_weak_
             }
         }
     }
-    PHASE_STAMP(6);
+    PHASE_STAMP(PS_P6);
 }
 
 // k_weak_cand_g's workgroups: 8 waves, wave h = anchor candidate h
@@ -3118,9 +2992,6 @@ __global__ __launch_bounds__(BLOCK) void k_gp_count(Args a, const int *__restric
 // its window anchor's segment, and every reference keeps its own (loc[WEAK index * 8 + k - 1]);
 // k_gp_place then writes each reference at segment offset + place -- no second pass of atomics
 // (k_gp_fill, the path APD_GP_FILL=1 keeps)
-#ifndef GP_LOC_BLOCK
-#define GP_LOC_BLOCK 1  // k_gp_count_loc: per-workgroup aggregation of the anchors' counts in LDS
-#endif
 #define GP_LOC_LG 12
 #define GP_LOC_HS (1 << GP_LOC_LG)  // >= 2 x the 8 * BLOCK references a workgroup can hold: load <= 0.5
 static_assert(GP_LOC_HS >= 2 * 8 * BLOCK, "k_gp_count_loc LDS table sizing");
@@ -3153,7 +3024,6 @@ __global__ __launch_bounds__(BLOCK) void k_gp_count_loc(Args a, const int *__res
     int pos[8];
     bool okk[8];
     int hl[8], rk[8];
-#if GP_LOC_BLOCK
     // The workgroup's references aggregated per window anchor in LDS first (the runs' lengths added
     // into a per-anchor local count, whose returned value is the run's offset within the workgroup),
     // then one global atomic per distinct anchor of the workgroup: neighbouring tiles share their
@@ -3195,21 +3065,6 @@ __global__ __launch_bounds__(BLOCK) void k_gp_count_loc(Args a, const int *__res
     uint32_t l[8];
 #pragma unroll
     for (int k = 0; k < 8; ++k) l[k] = (uint32_t)(hcnt[slot[k]] + pos[k]);  // (k_gp_place reads used windows only)
-#else
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        if (valid[k] && wst[k] == APD_STRONG) cb |= 1u << k;
-        okk[k] = valid[k] && (cid == 0 || lab[k] == cid);  // (gp_window_used)
-        if (okk[k]) wm |= 1u << k;
-        int len;
-        gp_run(okk[k], q[k], hl[k], rk[k], len);
-        pos[k] = 0;
-        if (okk[k] && rk[k] == 0) pos[k] = atomicAdd(&cnt[q[k]], len);
-    }
-    uint32_t l[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) l[k] = (uint32_t)(__shfl(pos[k], hl[k]) + rk[k]);  // (k_gp_place reads used windows only)
-#endif
     if (act) {
         uint4 *d = reinterpret_cast<uint4 *>(loc + (size_t)wi * 8);
         d[0] = make_uint4(l[0], l[1], l[2], l[3]);
@@ -3529,10 +3384,7 @@ __global__ __launch_bounds__(CHUNK) void k_gp_dedup_q(Args a, const int *__restr
 // range of pcost: the costs are staged in LDS ([pair][Np], gp_cost_lds_bytes) and written with
 // coalesced 16-byte stores after the view loop (a 4-byte store per (pair, view) at the row stride
 // wrote 4.2x the bytes, profiles/r3_pmc_k_gp_cost_c3b.json).
-#ifndef GP_COST_STAGED
-#define GP_COST_STAGED 1  // (A/B: 0 = one 4-byte store per (pair, view))
-#endif
-static inline size_t gp_cost_lds_bytes(int N) { return GP_COST_STAGED ? (size_t)BLOCK * ((N + 3) & ~3) * sizeof(float) : 0; }
+static inline size_t gp_cost_lds_bytes(int N) { return (size_t)BLOCK * ((N + 3) & ~3) * sizeof(float); }
 template <bool F16, bool SA>
 __global__ __launch_bounds__(BLOCK) void k_gp_cost(Args a, const int2 *__restrict__ plist, int np, float *__restrict__ pcost) {
     float *crow = apd_dyn_lds;  // [BLOCK][Np]
@@ -3570,11 +3422,9 @@ __global__ __launch_bounds__(BLOCK) void k_gp_cost(Args a, const int2 *__restric
             if (live) res = ncc_finalize_pre(R.inv(), R.srp(), R.var(), ss, sss, srs);
         }
         nlive += live;
-        if (GP_COST_STAGED) crow[threadIdx.x * Np + v] = res;
-        else if (act) pcost[(size_t)i * Np + v] = res;
+        crow[threadIdx.x * Np + v] = res;
     }
-    if (a.evals) wave_count(a.evals, 5, nlive);  // (profiling: pair windows evaluated)
-    if (!GP_COST_STAGED) return;
+    if (a.evals) wave_count(a.evals, EV_PAIR_WIN, nlive);  // (profiling: pair windows evaluated)
     for (int v = N; v < Np; ++v) crow[threadIdx.x * Np + v] = -1.0f;  // (padding, never read)
     __syncthreads();
     const int nq = (min(BLOCK, np - i0) * Np) >> 2;  // float4s of the block's rows
@@ -3707,7 +3557,7 @@ __global__ __launch_bounds__(PK_BLOCK, PK_MINW) void k_weak_cand_g(Args a, const
         // (k_weak_cand_comb reads it back and writes the candidate's cost in its place)
         if (want) out[cand_at(gm != 0, N, v, h, wc, wi1, first + p1)] = dead ? -1.0f : center_cost;
     }
-    if (a.evals) wave_count(a.evals, 6, nlive);  // (profiling: centre windows evaluated)
+    if (a.evals) wave_count(a.evals, EV_CAND_CENTRE_WIN, nlive);  // (profiling: centre windows evaluated)
 }
 // The focal combination (APD.cu:576-593, Softmax 431-446) of each (WEAK pixel, candidate) and view,
 // a thread per (pixel, candidate): few registers and many waves in flight for the pair-cost gathers.
@@ -3932,7 +3782,6 @@ __global__ __launch_bounds__(VM_BLOCK, VM_MINW) void k_depth_to_weak_vm(Args a, 
     const bool act = pv && L.active[p] != 0;
     const float base = L.base[p], disp = L.disp[p], wn = L.wn[p];
     const uint32_t sv = L.sel[p];
-    const float4 pl = L.pl[p];
     const float gf = a.gf;
     // Compacted (disparity, pixel) pairs: per view, only the active pixels that selected it (the
     // others' costs are never read), packed 64 to a wave-task, disparity-major, dealt round-robin over
@@ -4094,7 +3943,7 @@ __global__ __launch_bounds__(VM_BLOCK, VM_MINW) void k_depth_to_weak_vm(Args a, 
                 tcL[(dd * N + v) * VM_P + q] = tc;
             }
         }
-        if (a.evals) { wave_count(a.evals, 3, n_ncc); wave_count(a.evals, 4, n_geo); }
+        if (a.evals) { wave_count(a.evals, EV_DW_NCC, n_ncc); wave_count(a.evals, EV_DW_GEOM, n_geo); }
         __syncthreads();
         // ---- P2: in-order weighted view sums per (pixel, depth)
         for (int dd = wave; dd < dc; dd += VM_WAVES) {
@@ -4232,7 +4081,7 @@ __global__ __launch_bounds__(VM_BLOCK, VM_MINW) void k_random_init_vm(Args a, in
                         W->anc[k * VM_P + p] = ok ? ((int)(uint16_t)ap.x | ((int)ap.y << 16)) : -1;
                         if (ok && !(cid != 0 && sa_at_dev(a, ap.x, ap.y) != cid)) awin |= 1u << k;
                     }
-                    W->flags[p] = awin << 16;
+                    W->flags[p] = wvf_win_bits(awin);
                 }
                 wv_build_windows<F16>(a, *W, p, anc, cid, wave, VM_WAVES);
             }
@@ -4566,6 +4415,11 @@ void set_global_err(const std::string &s) {
 
 }  // namespace
 
+// apd_ctx::ev: the stage boundaries on the ctx stream (TE_INIT_END: on RandomInitialization's stream)
+enum TimingEv {
+    TE_PREP_BEGIN = 0, TE_ANCHORS_END = 1, TE_PAIRS_END = 2, TE_JOIN_END = 3, TE_ITER0 = 4,  // iterations 0..7: 4..11
+    TE_SWEEP_END = 12, TE_POST_END = 13, TE_LISTS_END = 14, TE_INIT_END = 15, TE_COUNT = 16
+};
 struct apd_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -4586,7 +4440,7 @@ struct apd_ctx {
     Args args{};
     bool loaded = false, prepared = false;
     int optional_fallbacks = 0;    // optional buffers try_ensure could not allocate
-    bool prep_timed = false;       // the prepare events (ev[0..3], ev[14], ev[15]) of the last apd_stage_prepare
+    bool prep_timed = false;       // the prepare events (all but the sweep's) of the last apd_stage_prepare
     int dw_tile_w = 8;             // DepthToWeak pixel tile width (64 / tile height); APD_DW_TILE_W
     int tile_w = 16;               // sweep list tile width (tile = tile_w x 256/tile_w positions); APD_TILE_W
                                    // (16 x 16: -1 % per C3 iteration against 8 x 32, profiles/r4_ab_tile_shape.txt)
@@ -4624,12 +4478,12 @@ struct apd_ctx {
     bool want_curve = false;
     apd_params params{};
     // timing
-    hipEvent_t ev[16] = {};
+    hipEvent_t ev[TE_COUNT] = {};
     apd_timing timing{};
     // profiling of the loop-body kernels (HIP events around each launch on the ctx stream)
     struct ProfEv {
         hipEvent_t e0, e1;
-        int kind;    // APD_PROF_STRONG_SWEEP, APD_PROF_RANSAC_FIT, APD_PROF_WEAK_CAND, APD_PROF_WEAK_SWEEP
+        int kind;    // an APD_PROF_* kernel kind (apd_hip.h; APD_PROF_WEAK_CAND is their sum, never recorded)
         int64_t px;  // pixels the launch covered
     };
     bool prof = false;
@@ -4733,26 +4587,18 @@ static int build_near_offsets(apd_ctx *ctx) {
 template <class T>
 static inline T devptr(const void *p) { return reinterpret_cast<T>(reinterpret_cast<uintptr_t>(p)); }
 
-// launch the fp16-pair or the fp32-quad instantiation of a sampling kernel
-#define LAUNCH_TEX(kern, grid, block, lds, stream, ...)                                            \
-    do {                                                                                         \
-        if (ctx->args.tex_f16) hipLaunchKernelGGL((kern<true>), grid, block, lds, stream, __VA_ARGS__); \
-        else hipLaunchKernelGGL((kern<false>), grid, block, lds, stream, __VA_ARGS__);            \
-    } while (0)
-
-// ... and of its SA-masked (SA quadrant windows on the fast taps) or unmasked form
-// (the same with a third template argument)
-#define LAUNCH_TEX_SA(kern, grid, block, lds, stream, ...)                                          \
-    do {                                                                                         \
-        const bool sa_ = ctx->args.sa_any != 0;                                                  \
-        if (ctx->args.tex_f16) {                                                                 \
-            if (sa_) hipLaunchKernelGGL((kern<true, true>), grid, block, lds, stream, __VA_ARGS__); \
-            else hipLaunchKernelGGL((kern<true, false>), grid, block, lds, stream, __VA_ARGS__);  \
-        } else {                                                                                 \
-            if (sa_) hipLaunchKernelGGL((kern<false, true>), grid, block, lds, stream, __VA_ARGS__); \
-            else hipLaunchKernelGGL((kern<false, false>), grid, block, lds, stream, __VA_ARGS__); \
-        }                                                                                        \
-    } while (0)
+// A kernel's runtime variants as template arguments: calls f once with one std::bool_constant per flag,
+// so a launch takes its kernel instantiation and its LDS size from the same arguments, e.g.
+//   with_flags([&](auto F16, auto SA) { hipLaunchKernelGGL((k<F16, SA>), ..., lds_bytes<F16, SA>(N), ...); },
+//              a.tex_f16 != 0, a.sa_any != 0);
+// (fp16 texel pairs or fp32 quads; SA-masked windows on the fast taps or not)
+template <class F>
+static inline void with_flags(F &&f) { f(); }
+template <class F, class... Rest>
+static inline void with_flags(F &&f, bool b, Rest... rest) {
+    if (b) with_flags([&](auto... bs) { f(std::true_type{}, bs...); }, rest...);
+    else with_flags([&](auto... bs) { f(std::false_type{}, bs...); }, rest...);
+}
 
 // The smallest non-negative float d with fl(d / D) >= t (IEEE single division, monotone in d for
 // D > 0), so that fl(d / D) < t <=> d < limit for every d >= 0 (NaN: false both ways). False when D
@@ -5171,7 +5017,6 @@ int32_t apd_set_problem(apd_ctx *ctx, const apd_problem *pb) {
     return APD_OK;
 }
 
-// device-side ordered compaction of one pixel set
 // Sweep lists (modes 0/1) in tile order: count per tile, scan, fill.
 static void tile_count_scan(apd_ctx *ctx, int mode, int colour, int *total_dev) {
     Args &a = ctx->args;
@@ -5192,17 +5037,17 @@ static int build_tile_list(apd_ctx *ctx, int mode, int colour, int *out, int *to
                        (const int *)ctx->rowoff.p, out, (quad && tile_quad_ok(tw)) ? 1 : 0);
     return check_launch(ctx, "tile list build");
 }
-// anchors_map (mode 2) in row-major order (APD.cpp:627-640)
-static int build_list(apd_ctx *ctx, int mode, int colour, int *out, int *total_dev) {
-    Args &a = ctx->args;
-    hipStream_t s = ctx->stream;
-    hipLaunchKernelGGL(k_list_count, dim3(a.H), dim3(BLOCK), 0, s, a, mode, colour, (int *)ctx->rowcnt.p);
-    hipLaunchKernelGGL(k_list_scan, dim3(1), dim3(1024), 0, s, (const int *)ctx->rowcnt.p, a.H, (int *)ctx->rowoff.p,
-                       total_dev);
-    hipLaunchKernelGGL(k_list_fill, dim3(a.H), dim3(BLOCK), 0, s, a, mode, colour, (const int *)ctx->rowoff.p, out);
-    return check_launch(ctx, "list build");
-}
 
+// the device counters of a profiled run (Args::evals), else null
+static APD_G unsigned long long *prof_evals(const apd_ctx *ctx) {
+    return (ctx->prof && ctx->evals.p) ? (APD_G unsigned long long *)ctx->evals.p : nullptr;
+}
+// workgroups of the kernels over dw_tile_w x (VM_P / dw_tile_w) pixel tiles (RandomInitialization,
+// DepthToWeak, LocalRefine)
+static unsigned pixel_tile_grid(const apd_ctx *ctx) {
+    const int tw = ctx->dw_tile_w, th = VM_P / tw;
+    return (unsigned)(((ctx->args.W + tw - 1) / tw) * ((ctx->args.H + th - 1) / th));
+}
 static int *list_ptr(apd_ctx *ctx, int which) {
     // 4 lists share one HW-sized buffer: [strong black][strong red][weak black][weak red] are disjoint
     // subsets of the pixels, so their concatenation never exceeds H*W entries.
@@ -5216,8 +5061,6 @@ static size_t wcand_bytes(int N, size_t wc, int nw) {
     return (size_t)N * 8 * std::max(wc, (size_t)blocks_for((size_t)nw, VM_P) * VM_P) * sizeof(float);
 }
 
-
-// exclusive prefix sum of n ints (rocPRIM) on the ctx stream
 // test hook (tests/test_gpu_cli.py): APD_TEST_LIB_ENOMEM_AT=k makes the k-th APD apd_stage_prepare of the
 // process fail as if its candidate-cost buffer did not fit -- after RandomInitialization was started on
 // a side stream, the early return the callers' release-and-retry must survive (drain())
@@ -5229,6 +5072,10 @@ static bool test_enomem_hook(apd_ctx *ctx) {
     return true;
 }
 
+// exclusive prefix sum of n ints (rocPRIM) on the ctx stream
+// (APD_ENOMEM: the temporary storage does not fit. The pair table is optional, so its builders return
+// pair_scan_status(st): gp_on stays false and nothing is reported)
+static inline int pair_scan_status(int st) { return st == APD_ENOMEM ? APD_OK : st; }
 static int exclusive_scan_int(apd_ctx *ctx, const int *in, int *out, size_t n) {
     size_t tb = 0;
     HIP_OK(ctx, rocprim::exclusive_scan(nullptr, tb, in, out, 0, n, rocprim::plus<int>(), ctx->stream));
@@ -5238,7 +5085,8 @@ static int exclusive_scan_int(apd_ctx *ctx, const int *in, int *out, size_t n) {
 }
 
 // The image-wide (window anchor, candidate anchor) pair table of the prepared problem (see
-// k_gp_dedup); ctx->gp_on stays false (k_weak_cand_vm's per-group pairs) when a buffer does not fit.
+// k_gp_dedup); ctx->gp_on stays false (the Weak sweep evaluates the anchor candidates itself, P1) when a buffer does
+// not fit.
 static int build_global_pairs(apd_ctx *ctx, int nw) {
     Args &a = ctx->args;
     hipStream_t s = ctx->stream;
@@ -5261,7 +5109,7 @@ static int build_global_pairs(apd_ctx *ctx, int nw) {
         hipLaunchKernelGGL(k_gp_count, dim3(blocks_for((size_t)nw, BLOCK)), dim3(BLOCK), 0, s, a, (const int *)ctx->wlist.p, nw, cnt,
                            (uint8_t *)ctx->gp_cb.p, (uint8_t *)ctx->gp_cb.p + wc);
     int st;
-    if ((st = exclusive_scan_int(ctx, cnt, cur, HW + 1))) return st == APD_ENOMEM ? APD_OK : st;
+    if ((st = exclusive_scan_int(ctx, cnt, cur, HW + 1))) return pair_scan_status(st);
     int nrefs = 0;
     HIP_OK(ctx, hipMemcpyAsync(&nrefs, cur + HW, sizeof(int), hipMemcpyDeviceToHost, s));
     if (ctx->gp_place) {
@@ -5279,7 +5127,7 @@ static int build_global_pairs(apd_ctx *ctx, int nw) {
         return APD_OK;
     int *tpos = (int *)ctx->gp_ccnt.p, *tasks = cnt;  // (the fill cursors are done with)
     hipLaunchKernelGGL(k_gp_flags, dim3(blocks_for(HW + 1, BLOCK)), dim3(BLOCK), 0, s, (const int *)cur, (int)HW, cnt);
-    if ((st = exclusive_scan_int(ctx, cnt, tpos, HW + 1))) return st == APD_ENOMEM ? APD_OK : st;
+    if ((st = exclusive_scan_int(ctx, cnt, tpos, HW + 1))) return pair_scan_status(st);
     hipLaunchKernelGGL(k_gp_tasks, dim3(blocks_for(HW, BLOCK)), dim3(BLOCK), 0, s, (const int *)cur, (const int *)tpos, (int)HW, tasks);
     int ntask = 0;
     HIP_OK(ctx, hipMemcpyAsync(&ntask, tpos + HW, sizeof(int), hipMemcpyDeviceToHost, s));
@@ -5294,19 +5142,17 @@ static int build_global_pairs(apd_ctx *ctx, int nw) {
         const size_t pcap = std::min<size_t>((size_t)nrefs * ctx->gp_cap_factor, (size_t)INT32_MAX);
         if (try_ensure(ctx, ctx->gp_plist, pcap * sizeof(int2))) {
             HIP_OK(ctx, hipMemsetAsync(acnt, 0, sizeof(int), s));
-            if (ctx->gp_small) {
-#define GP_DEDUP_ARGS                                                                                                        \
-    s, a, (const int *)tasks, (const int *)cur, (const uint32_t *)ctx->gp_refs.p, (const uint8_t *)ctx->gp_cb.p, acnt,      \
-        (const int *)nullptr, (int2 *)ctx->gp_plist.p, (uint32_t *)ctx->gp_pidx.p, (int)pcap
-                hipLaunchKernelGGL((k_gp_dedup<2, GP_SMALL_HS, WAVE, -1, GP_SMALL_N>), dim3(ntask), dim3(WAVE), 0, GP_DEDUP_ARGS);
-                hipLaunchKernelGGL((k_gp_dedup<2, GP_MEDIUM_HS, GP_CHUNK, GP_SMALL_N, GP_CHUNK>), dim3(ntask), dim3(GP_CHUNK), 0,
-                                   GP_DEDUP_ARGS);
-                hipLaunchKernelGGL((k_gp_dedup<2, GP_HS, GP_CHUNK, GP_CHUNK>), dim3(ntask), dim3(GP_CHUNK), 0, GP_DEDUP_ARGS);
-#undef GP_DEDUP_ARGS
-            } else {
-                hipLaunchKernelGGL((k_gp_dedup<2>), dim3(ntask), dim3(GP_CHUNK), 0, s, a, (const int *)tasks, (const int *)cur,
+            auto dedup = [&](auto kern, int block) {
+                hipLaunchKernelGGL(kern, dim3(ntask), dim3(block), 0, s, a, (const int *)tasks, (const int *)cur,
                                    (const uint32_t *)ctx->gp_refs.p, (const uint8_t *)ctx->gp_cb.p, acnt, (const int *)nullptr,
                                    (int2 *)ctx->gp_plist.p, (uint32_t *)ctx->gp_pidx.p, (int)pcap);
+            };
+            if (ctx->gp_small) {
+                dedup(k_gp_dedup<2, GP_SMALL_HS, WAVE, -1, GP_SMALL_N>, WAVE);
+                dedup(k_gp_dedup<2, GP_MEDIUM_HS, GP_CHUNK, GP_SMALL_N, GP_CHUNK>, GP_CHUNK);
+                dedup(k_gp_dedup<2, GP_HS, GP_CHUNK, GP_CHUNK>, GP_CHUNK);
+            } else {
+                dedup(k_gp_dedup<2>, GP_CHUNK);
             }
             HIP_OK(ctx, hipMemcpyAsync(&npairs, acnt, sizeof(int), hipMemcpyDeviceToHost, s));
             HIP_OK(ctx, hipStreamSynchronize(s));
@@ -5321,7 +5167,7 @@ static int build_global_pairs(apd_ctx *ctx, int nw) {
             hipLaunchKernelGGL((k_gp_dedup<0>), dim3(ntask), dim3(GP_CHUNK), 0, s, a, (const int *)tasks, (const int *)cur,
                                (const uint32_t *)ctx->gp_refs.p, (const uint8_t *)ctx->gp_cb.p, acnt, (const int *)nullptr,
                                (int2 *)nullptr, (uint32_t *)nullptr, 0);
-        if ((st = exclusive_scan_int(ctx, acnt, abase, (size_t)ntask + 1))) return st == APD_ENOMEM ? APD_OK : st;
+        if ((st = exclusive_scan_int(ctx, acnt, abase, (size_t)ntask + 1))) return pair_scan_status(st);
         HIP_OK(ctx, hipMemcpyAsync(&npairs, abase + ntask, sizeof(int), hipMemcpyDeviceToHost, s));
         HIP_OK(ctx, hipStreamSynchronize(s));
         if (npairs > 0 && !try_ensure(ctx, ctx->gp_plist, (size_t)npairs * sizeof(int2))) return APD_OK;
@@ -5344,6 +5190,20 @@ static int build_global_pairs(apd_ctx *ctx, int nw) {
 // capacity is an upper bound from the WEAK count. apd_stage_prepare's end (finish_global_pairs) reads
 // the pair count back once, allocates the costs, and rebuilds the table with the synchronous path
 // above if a bound was exceeded.
+// gp_cls of the async table: the class lists 0 / 1 (small / medium anchors, U + 1 ints each), the
+// class-2 runs (2 * cap2 ints), then 8 counters ctr: [0..2] class counts, [3] next, [4] overflow, [5] pairs
+struct GpClsLayout {
+    size_t U;     // most anchors there can be: the pixels that are not WEAK
+    size_t cap2;  // class-2 runs: <= anchors + references / GP_SPLIT
+    size_t list(int c) const { return (size_t)c * (U + 1); }
+    size_t ctr() const { return 2 * (U + 1) + 2 * cap2; }
+    size_t ints() const { return ctr() + 8; }
+};
+static GpClsLayout gp_cls_layout(const apd_ctx *ctx, int nw) {
+    const size_t HW = (size_t)ctx->args.HW, weak = (size_t)ctx->weak_count;
+    const size_t U = HW > weak ? HW - weak : 1;
+    return {U, U + 1 + (size_t)nw * 8 / GP_SPLIT + 1};
+}
 static int build_global_pairs_async(apd_ctx *ctx, int nw) {
     Args &a = ctx->args;
     hipStream_t s = ctx->stream;
@@ -5351,37 +5211,36 @@ static int build_global_pairs_async(apd_ctx *ctx, int nw) {
     ctx->gp_on = false;
     ctx->gp_np = 0;
     ctx->gp_pending = false;
-    const size_t U = HW > (size_t)ctx->weak_count ? HW - (size_t)ctx->weak_count : 1;  // anchors: STRONG pixels
-    const size_t cap2 = U + 1 + (size_t)nw * 8 / GP_SPLIT + 1;  // class-2 runs: <= anchors + references / GP_SPLIT
+    const GpClsLayout cl = gp_cls_layout(ctx, nw);
     const size_t pcap = std::min<size_t>((size_t)nw * 4 * (size_t)ctx->gp_cap_factor, (size_t)INT32_MAX);
     if (!try_ensure(ctx, ctx->gp_cnt, (HW + 1) * sizeof(int)) || !try_ensure(ctx, ctx->gp_cur, (HW + 1) * sizeof(int)) ||
         !try_ensure(ctx, ctx->gp_refs, (size_t)nw * 8 * sizeof(uint32_t)) ||
         !try_ensure(ctx, ctx->gp_pidx, wc * 64 * sizeof(uint32_t)) || !try_ensure(ctx, ctx->gp_cb, 2 * wc) ||
-        !try_ensure(ctx, ctx->gp_cls, (2 * (U + 1) + 2 * cap2 + 8) * sizeof(int)) ||
+        !try_ensure(ctx, ctx->gp_cls, cl.ints() * sizeof(int)) ||
         !try_ensure(ctx, ctx->gp_plist, std::max<size_t>(pcap, 1) * sizeof(int2)))
         return APD_OK;
     int *cnt = (int *)ctx->gp_cnt.p, *cur = (int *)ctx->gp_cur.p;
-    int *lists = (int *)ctx->gp_cls.p, *ctr = lists + 2 * (U + 1) + 2 * cap2;  // ctr: [3] class counts, [3] next, [4] overflow, [5] pairs
+    int *lists = (int *)ctx->gp_cls.p, *ctr = lists + cl.ctr();
     uint32_t *loc = (uint32_t *)ctx->gp_pidx.p;
     HIP_OK(ctx, hipMemsetAsync(cnt, 0, (HW + 1) * sizeof(int), s));
     HIP_OK(ctx, hipMemsetAsync(ctr, 0, 8 * sizeof(int), s));
     hipLaunchKernelGGL(k_gp_count_loc, dim3(blocks_for((size_t)nw, BLOCK)), dim3(BLOCK), 0, s, a, (const int *)ctx->wlist.p, nw,
                        cnt, (uint8_t *)ctx->gp_cb.p, (uint8_t *)ctx->gp_cb.p + wc, loc);
     int st;
-    if ((st = exclusive_scan_int(ctx, cnt, cur, HW + 1))) return st == APD_ENOMEM ? APD_OK : st;
+    if ((st = exclusive_scan_int(ctx, cnt, cur, HW + 1))) return pair_scan_status(st);
     hipLaunchKernelGGL(k_gp_place, dim3(blocks_for((size_t)nw, BLOCK)), dim3(BLOCK), 0, s, a, (const int *)ctx->wlist.p, nw,
                        (const int *)cur, (const uint8_t *)ctx->gp_cb.p + wc, (const uint32_t *)loc, (uint32_t *)ctx->gp_refs.p);
-    hipLaunchKernelGGL(k_gp_classes, dim3(blocks_for(HW, BLOCK)), dim3(BLOCK), 0, s, (const int *)cur, (int)HW, (int)(U + 1),
-                       (int)cap2, lists, ctr);
+    hipLaunchKernelGGL(k_gp_classes, dim3(blocks_for(HW, BLOCK)), dim3(BLOCK), 0, s, (const int *)cur, (int)HW, (int)(cl.U + 1),
+                       (int)cl.cap2, lists, ctr);
     const int ncu = ctx->ncu;
-#define GP_Q_ARGS(c)                                                                                                         \
-    s, a, (const int *)(lists + (size_t)(c) * (U + 1)), (const int *)(ctr + (c)), ctr + 3, (const int *)cur,                \
-        (const uint32_t *)ctx->gp_refs.p, (const uint8_t *)ctx->gp_cb.p, ctr + 5, (int2 *)ctx->gp_plist.p,                  \
-        (uint32_t *)ctx->gp_pidx.p, (int)pcap
-    hipLaunchKernelGGL((k_gp_dedup_q<GP_SMALL_HS, WAVE, false>), dim3(ncu * 32), dim3(WAVE), 0, GP_Q_ARGS(0));
-    hipLaunchKernelGGL((k_gp_dedup_q<GP_MEDIUM_HS, GP_CHUNK, false>), dim3(ncu * 6), dim3(GP_CHUNK), 0, GP_Q_ARGS(1));
-    hipLaunchKernelGGL((k_gp_dedup_q<GP_HS, GP_CHUNK, true>), dim3(ncu * 3), dim3(GP_CHUNK), 0, GP_Q_ARGS(2));
-#undef GP_Q_ARGS
+    auto dedup_class = [&](auto kern, int c, int per_cu, int block) {
+        hipLaunchKernelGGL(kern, dim3(ncu * per_cu), dim3(block), 0, s, a, (const int *)(lists + cl.list(c)), (const int *)(ctr + c),
+                           ctr + 3, (const int *)cur, (const uint32_t *)ctx->gp_refs.p, (const uint8_t *)ctx->gp_cb.p, ctr + 5,
+                           (int2 *)ctx->gp_plist.p, (uint32_t *)ctx->gp_pidx.p, (int)pcap);
+    };
+    dedup_class(k_gp_dedup_q<GP_SMALL_HS, WAVE, false>, 0, 32, WAVE);
+    dedup_class(k_gp_dedup_q<GP_MEDIUM_HS, GP_CHUNK, false>, 1, 6, GP_CHUNK);
+    dedup_class(k_gp_dedup_q<GP_HS, GP_CHUNK, true>, 2, 3, GP_CHUNK);
     if ((st = check_launch(ctx, "pair table"))) return st;
     ctx->gp_pending = true;
     ctx->gp_on = true;
@@ -5394,10 +5253,7 @@ static int build_global_pairs_async(apd_ctx *ctx, int nw) {
 static int finish_global_pairs(apd_ctx *ctx, int nw) {
     if (!ctx->gp_pending) return APD_OK;
     ctx->gp_pending = false;
-    const size_t HW = (size_t)ctx->args.HW;
-    const size_t U = HW > (size_t)ctx->weak_count ? HW - (size_t)ctx->weak_count : 1;
-    const size_t cap2 = U + 1 + (size_t)nw * 8 / GP_SPLIT + 1;
-    const int *ctr = (const int *)ctx->gp_cls.p + 2 * (U + 1) + 2 * cap2;
+    const int *ctr = (const int *)ctx->gp_cls.p + gp_cls_layout(ctx, nw).ctr();
     int h[8] = {};
     HIP_OK(ctx, hipMemcpyAsync(h, ctr, 8 * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
     HIP_OK(ctx, hipStreamSynchronize(ctx->stream));
@@ -5426,7 +5282,7 @@ int32_t apd_stage_prepare(apd_ctx *ctx) {
     const unsigned gpx = blocks_for((size_t)a.HW, BLOCK);
     int st;
     ctx->gp_on = false;
-    (void)hipEventRecord(ctx->ev[0], s);
+    (void)hipEventRecord(ctx->ev[TE_PREP_BEGIN], s);
     if (a.use_apd) {
         // anchors_map from the input WEAK mask (APD.cpp:627-640). The reference numbers the WEAK pixels
         // row-major; here they are numbered in the sweep lists' tile order, so the per-WEAK-pixel
@@ -5445,7 +5301,7 @@ int32_t apd_stage_prepare(apd_ctx *ctx) {
         }
         {
             Args ag = a;  // (profiling counters: instrumented builds of k_gen_anchors only)
-            ag.evals = (ctx->prof && ctx->evals.p) ? (APD_G unsigned long long *)ctx->evals.p : nullptr;
+            ag.evals = prof_evals(ctx);
             // the RANSAC in its own kernel when the stage fits (GA_STAGE_W words per WEAK pixel); else in k_gen_anchors
             const size_t wc = (size_t)std::max(ctx->weak_count, 1);
             uint32_t *stage = (ctx->ga_split && ctx->weak_count > 0 &&
@@ -5462,7 +5318,7 @@ int32_t apd_stage_prepare(apd_ctx *ctx) {
         hipLaunchKernelGGL(k_neighbour_update, dim3(gpx), dim3(BLOCK), 0, s, a);
         if ((st = check_launch(ctx, "anchors"))) return st;
     }
-    (void)hipEventRecord(ctx->ev[1], s);
+    (void)hipEventRecord(ctx->ev[TE_ANCHORS_END], s);
     // RandomInitialization needs the anchors and the input state only: with overlap it runs on side
     // stream 0 beside the lists and the pair table (which read neither what it writes -- planes,
     // costs, the next selections, view weights, kept costs -- nor write what it reads)
@@ -5473,27 +5329,14 @@ int32_t apd_stage_prepare(apd_ctx *ctx) {
         sri = ctx->side[0];
     }
     {
-        const int tw = ctx->dw_tile_w, th = VM_P / tw;
-        const unsigned nb = (unsigned)(((a.W + tw - 1) / tw) * ((a.H + th - 1) / th));
-        if (a.use_apd) {
-            if (a.sa_any) {
-                if (a.tex_f16) hipLaunchKernelGGL((k_random_init_vm<true, true, true>), dim3(nb), dim3(VM_BLOCK), (ri_lds_bytes<true, true>(a.N) + sa_lds_bytes(a)), sri, a, tw);
-                else hipLaunchKernelGGL((k_random_init_vm<false, true, true>), dim3(nb), dim3(VM_BLOCK), (ri_lds_bytes<false, true>(a.N) + sa_lds_bytes(a)), sri, a, tw);
-            } else {
-                if (a.tex_f16) hipLaunchKernelGGL((k_random_init_vm<true, true, false>), dim3(nb), dim3(VM_BLOCK), (ri_lds_bytes<true, true>(a.N)), sri, a, tw);
-                else hipLaunchKernelGGL((k_random_init_vm<false, true, false>), dim3(nb), dim3(VM_BLOCK), (ri_lds_bytes<false, true>(a.N)), sri, a, tw);
-            }
-        } else {
-            if (a.sa_any) {
-                if (a.tex_f16) hipLaunchKernelGGL((k_random_init_vm<true, false, true>), dim3(nb), dim3(VM_BLOCK), (ri_lds_bytes<true, false>(a.N) + sa_lds_bytes(a)), sri, a, tw);
-                else hipLaunchKernelGGL((k_random_init_vm<false, false, true>), dim3(nb), dim3(VM_BLOCK), (ri_lds_bytes<false, false>(a.N) + sa_lds_bytes(a)), sri, a, tw);
-            } else {
-                if (a.tex_f16) hipLaunchKernelGGL((k_random_init_vm<true, false, false>), dim3(nb), dim3(VM_BLOCK), (ri_lds_bytes<true, false>(a.N)), sri, a, tw);
-                else hipLaunchKernelGGL((k_random_init_vm<false, false, false>), dim3(nb), dim3(VM_BLOCK), (ri_lds_bytes<false, false>(a.N)), sri, a, tw);
-            }
-        }
+        const int tw = ctx->dw_tile_w;
+        const unsigned nb = pixel_tile_grid(ctx);
+        with_flags([&](auto F16, auto APD, auto SA) {
+            hipLaunchKernelGGL((k_random_init_vm<F16, APD, SA>), dim3(nb), dim3(VM_BLOCK), (ri_lds_bytes<F16, APD>(a.N)) + sa_lds_bytes(a),
+                               sri, a, tw);
+        }, a.tex_f16 != 0, a.use_apd != 0, a.sa_any != 0);
         if ((st = check_launch(ctx, "k_random_init"))) return st;
-        (void)hipEventRecord(ctx->ev[15], sri);  // (apd_timing.init_ms = ev[1] -> ev[15])
+        (void)hipEventRecord(ctx->ev[TE_INIT_END], sri);  // (apd_timing.init_ms = TE_ANCHORS_END -> TE_INIT_END)
         if (ctx->overlap) HIP_OK(ctx, hipEventRecord(ctx->ev_side[0], sri));
     }
     // pixel lists for the sweeps (after NeigbourUpdate)
@@ -5522,7 +5365,7 @@ int32_t apd_stage_prepare(apd_ctx *ctx) {
             const size_t wc = (size_t)std::max(ctx->weak_count, 1);
             if (test_enomem_hook(ctx)) return APD_ENOMEM;  // (RandomInitialization is in flight on side stream 0)
             if ((st = ensure(ctx, ctx->wcand, wcand_bytes(a.N, wc, nw)))) return st;
-            (void)hipEventRecord(ctx->ev[14], s);
+            (void)hipEventRecord(ctx->ev[TE_LISTS_END], s);
             // (the table's keys hold a pixel index below 2^25 and x below 2^15; else the sweep
             // evaluates the candidates itself)
             // (a pair packs x | filtered << 15 | y << 16 into an int: H < 32768 is also apd_set_problem's limit)
@@ -5531,7 +5374,7 @@ int32_t apd_stage_prepare(apd_ctx *ctx) {
                                     : build_global_pairs(ctx, ctx->cnt[2] + ctx->cnt[3])))
                 return st;
         } else {
-            (void)hipEventRecord(ctx->ev[14], s);
+            (void)hipEventRecord(ctx->ev[TE_LISTS_END], s);
         }
         // the anchor windows' reference side (k_anchor_rec: taps, tap mask, finalisation terms; 32 B
         // with fp16 taps, else 64 B, per pixel and SA variant), built only when k_gp_cost reads it.
@@ -5552,10 +5395,10 @@ int32_t apd_stage_prepare(apd_ctx *ctx) {
             }
         }
     }
-    (void)hipEventRecord(ctx->ev[2], s);
+    (void)hipEventRecord(ctx->ev[TE_PAIRS_END], s);
     if (ctx->overlap) HIP_OK(ctx, hipStreamWaitEvent(s, ctx->ev_side[0], 0));  // join RandomInitialization
     HIP_OK(ctx, hipMemcpyAsync(ctx->sel.p, ctx->sel2.p, (size_t)a.HW * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
-    (void)hipEventRecord(ctx->ev[3], s);
+    (void)hipEventRecord(ctx->ev[TE_JOIN_END], s);
     if ((st = finish_global_pairs(ctx, ctx->cnt[2] + ctx->cnt[3]))) return st;
     ctx->prep_timed = true;
     ctx->wcur_fresh = a.wcur != nullptr;
@@ -5598,7 +5441,7 @@ int32_t apd_stage_iteration(apd_ctx *ctx, int32_t iter) {
     Args &a = ctx->args;
     hipStream_t s = ctx->stream;
     int st;
-    APD_G unsigned long long *evals = (ctx->prof && ctx->evals.p) ? (APD_G unsigned long long *)ctx->evals.p : nullptr;
+    APD_G unsigned long long *evals = prof_evals(ctx);
     for (int colour = 0; colour < 2; ++colour) {
         const int n = ctx->cnt[colour];
         if (n <= 0) continue;
@@ -5606,8 +5449,10 @@ int32_t apd_stage_iteration(apd_ctx *ctx, int32_t iter) {
         Args ak = a;
         ak.evals = evals;
         if (!(ctx->wcur_fresh && iter == 0)) ak.wcur = nullptr;  // RandomInitialization's costs: iteration 0 only
-        LAUNCH_TEX_SA(k_sweep_strong_vm, dim3(blocks_for((size_t)n, VM_P)), dim3(VM_BLOCK), vm_lds_bytes(a.N, ctx->args.tex_f16 != 0) + sa_lds_bytes(a), s,
-                      ak, (const int *)list_ptr(ctx, colour), n, iter);
+        with_flags([&](auto F16, auto SA) {
+            hipLaunchKernelGGL((k_sweep_strong_vm<F16, SA>), dim3(blocks_for((size_t)n, VM_P)), dim3(VM_BLOCK),
+                               vm_lds_bytes<F16>(a.N) + sa_lds_bytes(a), s, ak, (const int *)list_ptr(ctx, colour), n, iter);
+        }, a.tex_f16 != 0, a.sa_any != 0);
         prof_end(ctx, e0, APD_PROF_STRONG_SWEEP, n);
         if ((st = check_launch(ctx, "k_sweep_strong"))) return st;
     }
@@ -5646,14 +5491,19 @@ int32_t apd_stage_iteration(apd_ctx *ctx, int32_t iter) {
             {
                 hipEvent_t e1 = prof_begin(ctx, sg);
                 if (ctx->gp_np > 0)
-                    LAUNCH_TEX_SA(k_gp_cost, dim3(blocks_for((size_t)ctx->gp_np, BLOCK)), dim3(BLOCK), gp_cost_lds_bytes(a.N), sg, ac,
-                               (const int2 *)ctx->gp_plist.p, ctx->gp_np, (float *)ctx->gp_pcost.p);
+                    with_flags([&](auto F16, auto SA) {
+                        hipLaunchKernelGGL((k_gp_cost<F16, SA>), dim3(blocks_for((size_t)ctx->gp_np, BLOCK)), dim3(BLOCK),
+                                           gp_cost_lds_bytes(a.N), sg, ac, (const int2 *)ctx->gp_plist.p, ctx->gp_np,
+                                           (float *)ctx->gp_pcost.p);
+                    }, a.tex_f16 != 0, a.sa_any != 0);
                 prof_end(ctx, e1, APD_PROF_GP_COST, ctx->gp_np, sg);
                 if (centre_kernel) {
                     if (ctx->overlap) HIP_OK(ctx, hipEventRecord(ctx->ev_side[1], sg));
                     e1 = prof_begin(ctx);
-                    LAUNCH_TEX_SA(k_weak_cand_g, dim3(blocks_for((size_t)nw, VM_P)), dim3(PK_BLOCK), 0, s, ac, (const int *)ctx->wlist.p, nw,
-                                  (const uint8_t *)ctx->gp_cb.p, (float *)ctx->wcand.p, wc, gm);
+                    with_flags([&](auto F16, auto SA) {
+                        hipLaunchKernelGGL((k_weak_cand_g<F16, SA>), dim3(blocks_for((size_t)nw, VM_P)), dim3(PK_BLOCK), 0, s, ac,
+                                           (const int *)ctx->wlist.p, nw, (const uint8_t *)ctx->gp_cb.p, (float *)ctx->wcand.p, wc, gm);
+                    }, a.tex_f16 != 0, a.sa_any != 0);
                     prof_end(ctx, e1, APD_PROF_WEAK_CAND_G, nw);
                     if (ctx->overlap) HIP_OK(ctx, hipStreamWaitEvent(s, ctx->ev_side[1], 0));  // join k_gp_cost
                 }
@@ -5694,11 +5544,11 @@ int32_t apd_stage_iteration(apd_ctx *ctx, int32_t iter) {
             e0 = prof_begin(ctx);
             // k_sweep_weak_vm's small cost table when every pixel's candidates are in `cand`
             const bool direct = cand != nullptr;
-            LAUNCH_TEX_SA(k_sweep_weak_vm, dim3(blocks_for((size_t)n, VM_P)), dim3(WV_BLOCK),
-                          (ctx->args.tex_f16 ? (ctx->args.sa_any ? wv_lds_bytes<true, 9, true>(a.N, direct) : wv_lds_bytes<true, 9, false>(a.N, direct))
-                                             : (ctx->args.sa_any ? wv_lds_bytes<false, 9, true>(a.N, direct) : wv_lds_bytes<false, 9, false>(a.N, direct))),
-                          s,
-                          aw, wl, n, iter, cand, wc, gm, (direct && !centre_kernel) ? 1 : 0, ctx->geom_tail ? 1 : 0);
+            with_flags([&](auto F16, auto SA) {
+                hipLaunchKernelGGL((k_sweep_weak_vm<F16, SA>), dim3(blocks_for((size_t)n, VM_P)), dim3(WV_BLOCK),
+                                   (wv_lds_bytes<F16, 9, SA>(a.N, direct)), s, aw, wl, n, iter, cand, wc, gm,
+                                   (direct && !centre_kernel) ? 1 : 0, ctx->geom_tail ? 1 : 0);
+            }, a.tex_f16 != 0, a.sa_any != 0);
             prof_end(ctx, e0, APD_PROF_WEAK_SWEEP, n);
         }
         prof_end(ctx, ewp, APD_PROF_WEAK_PATH, ctx->cnt[2] + ctx->cnt[3]);
@@ -5733,46 +5583,50 @@ int32_t apd_stage_finish(apd_ctx *ctx) {
         a.lr_geo = a.geom ? devptr<decltype(a.lr_geo)>((float *)ctx->lrs.p + plane) : nullptr;
     }
     {
-        const int tw = ctx->dw_tile_w, th = VM_P / tw;
-        const unsigned nb = (unsigned)(((a.W + tw - 1) / tw) * ((a.H + th - 1) / th));
+        const int tw = ctx->dw_tile_w;
+        const unsigned nb = pixel_tile_grid(ctx);
         const int dwc = dw_chunk(a.N, a.geom != 0, sa_lds_bytes(a));
         Args ad = a;
-        ad.evals = (ctx->prof && ctx->evals.p) ? (APD_G unsigned long long *)ctx->evals.p : nullptr;
+        ad.evals = prof_evals(ctx);
         // fp16 problems: DepthToWeak's taps over the pre-differenced texels (FastTexD, apd_set_problem)
         const bool dp = a.dpairs != nullptr;
         hipEvent_t e0 = prof_begin(ctx);
-        if (dp) {
-            const size_t lds = dw_lds_bytes(a.N, a.geom != 0, dwc) + sa_lds_bytes(a);
-            if (a.sa_any) hipLaunchKernelGGL((k_depth_to_weak_vm<true, true, true>), dim3(nb), dim3(VM_BLOCK), lds, s, ad, dwc, tw);
-            else hipLaunchKernelGGL((k_depth_to_weak_vm<true, false, true>), dim3(nb), dim3(VM_BLOCK), lds, s, ad, dwc, tw);
-        } else {
-            LAUNCH_TEX_SA(k_depth_to_weak_vm, dim3(nb), dim3(VM_BLOCK), dw_lds_bytes(a.N, a.geom != 0, dwc) + sa_lds_bytes(a), s, ad, dwc, tw);
-        }
+        const size_t lds = dw_lds_bytes(a.N, a.geom != 0, dwc) + sa_lds_bytes(a);
+        with_flags([&](auto F16, auto SA) {
+            if (dp) {  // (a.dpairs is set for fp16 problems only: apd_set_problem)
+                if constexpr (F16) hipLaunchKernelGGL((k_depth_to_weak_vm<true, SA, true>), dim3(nb), dim3(VM_BLOCK), lds, s, ad, dwc, tw);
+            } else {
+                hipLaunchKernelGGL((k_depth_to_weak_vm<F16, SA>), dim3(nb), dim3(VM_BLOCK), lds, s, ad, dwc, tw);
+            }
+        }, a.tex_f16 != 0, a.sa_any != 0);
         prof_end(ctx, e0, APD_PROF_DEPTH_TO_WEAK, a.HW);
     }
     if (a.geom || a.use_apd) hipLaunchKernelGGL(k_confidence, dim3(gpx), dim3(BLOCK), 0, s, a);
     {
-        const int tw = ctx->dw_tile_w, th = VM_P / tw;
-        const unsigned nb = (unsigned)(((a.W + tw - 1) / tw) * ((a.H + th - 1) / th));
-        LAUNCH_TEX_SA(k_local_refine_vm, dim3(nb), dim3(VM_BLOCK), lr_lds_bytes(a.N) + sa_lds_bytes(a), s, a, lr_chunk(a.N), tw);
+        const int tw = ctx->dw_tile_w;
+        const unsigned nb = pixel_tile_grid(ctx);
+        with_flags([&](auto F16, auto SA) {
+            hipLaunchKernelGGL((k_local_refine_vm<F16, SA>), dim3(nb), dim3(VM_BLOCK), lr_lds_bytes(a.N) + sa_lds_bytes(a), s, a,
+                               lr_chunk(a.N), tw);
+        }, a.tex_f16 != 0, a.sa_any != 0);
     }
     if ((st = check_launch(ctx, "finish"))) return st;
     return APD_OK;
 }
 
-// the prepare phase's fields of apd_timing from its events (the ctx stream has passed ev[3]).
+// the prepare phase's fields of apd_timing from its events (the ctx stream has passed TE_JOIN_END).
 // RandomInitialization runs first after the anchors, beside the lists and the pair table when the
 // ctx overlaps (side stream 0): init_ms is its own duration, lists_ms + pairs_ms the ctx stream's,
 // join_ms the ctx stream's wait for it, and anchors + lists + pairs + join == prepare.
 static void prepare_timing(apd_ctx *ctx, apd_timing &t) {
     memset(&t, 0, sizeof(t));
     if (!ctx->prep_timed) return;
-    (void)hipEventElapsedTime(&t.anchors_ms, ctx->ev[0], ctx->ev[1]);
-    (void)hipEventElapsedTime(&t.lists_ms, ctx->ev[1], ctx->ev[14]);
-    (void)hipEventElapsedTime(&t.pairs_ms, ctx->ev[14], ctx->ev[2]);
-    (void)hipEventElapsedTime(&t.join_ms, ctx->ev[2], ctx->ev[3]);
-    (void)hipEventElapsedTime(&t.prepare_ms, ctx->ev[0], ctx->ev[3]);
-    (void)hipEventElapsedTime(&t.init_ms, ctx->ev[1], ctx->ev[15]);
+    (void)hipEventElapsedTime(&t.anchors_ms, ctx->ev[TE_PREP_BEGIN], ctx->ev[TE_ANCHORS_END]);
+    (void)hipEventElapsedTime(&t.lists_ms, ctx->ev[TE_ANCHORS_END], ctx->ev[TE_LISTS_END]);
+    (void)hipEventElapsedTime(&t.pairs_ms, ctx->ev[TE_LISTS_END], ctx->ev[TE_PAIRS_END]);
+    (void)hipEventElapsedTime(&t.join_ms, ctx->ev[TE_PAIRS_END], ctx->ev[TE_JOIN_END]);
+    (void)hipEventElapsedTime(&t.prepare_ms, ctx->ev[TE_PREP_BEGIN], ctx->ev[TE_JOIN_END]);
+    (void)hipEventElapsedTime(&t.init_ms, ctx->ev[TE_ANCHORS_END], ctx->ev[TE_INIT_END]);
 }
 
 int32_t apd_get_prepare_timing(apd_ctx *ctx, apd_timing *timing) {
@@ -5792,21 +5646,21 @@ int32_t apd_run_patchmatch(apd_ctx *ctx) {
     if ((st = apd_stage_prepare(ctx))) return st;
     const int iters = ctx->params.max_iterations;
     for (int i = 0; i < iters; ++i) {
-        if (i < 8) (void)hipEventRecord(ctx->ev[4 + i], s);
+        if (i < 8) (void)hipEventRecord(ctx->ev[TE_ITER0 + i], s);
         if ((st = apd_stage_iteration(ctx, i))) return st;
     }
-    (void)hipEventRecord(ctx->ev[12], s);
+    (void)hipEventRecord(ctx->ev[TE_SWEEP_END], s);
     if ((st = apd_stage_finish(ctx))) return st;
-    (void)hipEventRecord(ctx->ev[13], s);
+    (void)hipEventRecord(ctx->ev[TE_POST_END], s);
     HIP_OK(ctx, hipStreamSynchronize(s));
     apd_timing &t = ctx->timing;
     prepare_timing(ctx, t);
-    (void)hipEventElapsedTime(&t.total_ms, ctx->ev[0], ctx->ev[13]);
-    (void)hipEventElapsedTime(&t.sweep_ms, ctx->ev[3], ctx->ev[12]);
-    (void)hipEventElapsedTime(&t.post_ms, ctx->ev[12], ctx->ev[13]);
+    (void)hipEventElapsedTime(&t.total_ms, ctx->ev[TE_PREP_BEGIN], ctx->ev[TE_POST_END]);
+    (void)hipEventElapsedTime(&t.sweep_ms, ctx->ev[TE_JOIN_END], ctx->ev[TE_SWEEP_END]);
+    (void)hipEventElapsedTime(&t.post_ms, ctx->ev[TE_SWEEP_END], ctx->ev[TE_POST_END]);
     const int ni = std::min(iters, 8);
     for (int i = 0; i < ni; ++i)
-        (void)hipEventElapsedTime(&t.iter_ms[i], ctx->ev[4 + i], (i + 1 < ni) ? ctx->ev[5 + i] : ctx->ev[12]);
+        (void)hipEventElapsedTime(&t.iter_ms[i], ctx->ev[TE_ITER0 + i], (i + 1 < ni) ? ctx->ev[TE_ITER0 + i + 1] : ctx->ev[TE_SWEEP_END]);
     t.iterations = iters;
     return APD_OK;
 }
