@@ -234,7 +234,21 @@ EVAL_EXPORTS = ["apd_eval_create", "apd_eval_destroy", "apd_eval_last_error", "a
                 "apd_eval_distances", "apd_eval_voxel_downsample", "apd_eval_get_timing",
                 "apd_eval_render_depth", "apd_eval_visibility", "apd_eval_get_render_timing",
                 "apd_eval_cube_cameras", "apd_eval_free_gap", "apd_eval_voxel_scores",
-                "apd_eval_get_protocol_timing"]
+                "apd_eval_get_protocol_timing",
+                "apd_eval_crop_volume", "apd_eval_crop_volume_host", "apd_eval_nearest", "apd_eval_nearest_host",
+                "apd_eval_transform", "apd_eval_transform_host", "apd_eval_register", "apd_eval_register_host",
+                "apd_eval_register_sums", "apd_eval_register_sums_host", "apd_eval_get_register_timing"]
+REG_BLOCK = 1024  # APD_EVAL_REG_BLOCK
+REG_SUMS = 19
+
+
+class ApdEvalRegInfo(C.Structure):  # include/apd_eval.h
+    _fields_ = [("iterations", C.c_int32), ("reserved", C.c_int32), ("n_corr", C.c_int64), ("n_finite", C.c_int64),
+                ("fitness", C.c_double), ("rmse", C.c_double)]
+
+    def as_dict(self) -> dict:
+        return {"iterations": self.iterations, "n_corr": self.n_corr, "n_finite": self.n_finite,
+                "fitness": self.fitness, "rmse": self.rmse}
 
 # include/apd_prep.h
 PREP_EXPORTS = ["apd_prep_create", "apd_prep_destroy", "apd_prep_last_error", "apd_prep_set_model",
@@ -386,6 +400,36 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
                                           C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.apd_eval_get_protocol_timing.restype = C.c_int32
     lib.apd_eval_get_protocol_timing.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    crop_tail = [C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_double, C.c_double, C.c_int32, C.c_void_p,
+                 C.c_void_p, C.c_void_p]
+    lib.apd_eval_crop_volume.restype = C.c_int32
+    lib.apd_eval_crop_volume.argtypes = [C.c_void_p] + crop_tail
+    lib.apd_eval_crop_volume_host.restype = C.c_int32
+    lib.apd_eval_crop_volume_host.argtypes = crop_tail
+    lib.apd_eval_nearest.restype = C.c_int32
+    lib.apd_eval_nearest.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]
+    lib.apd_eval_nearest_host.restype = C.c_int32
+    lib.apd_eval_nearest_host.argtypes = [C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_float, C.c_void_p,
+                                          C.c_void_p]
+    lib.apd_eval_transform.restype = C.c_int32
+    lib.apd_eval_transform.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.apd_eval_transform_host.restype = C.c_int32
+    lib.apd_eval_transform_host.argtypes = [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
+    reg_tail = [C.c_int64, C.c_void_p, C.c_void_p, C.c_float, C.c_int32, C.c_int32, C.c_double, C.c_double,
+                C.c_void_p, C.POINTER(ApdEvalRegInfo)]
+    lib.apd_eval_register.restype = C.c_int32
+    lib.apd_eval_register.argtypes = [C.c_void_p] + reg_tail
+    lib.apd_eval_register_host.restype = C.c_int32
+    lib.apd_eval_register_host.argtypes = [C.c_int64, C.c_void_p] + reg_tail
+    lib.apd_eval_register_sums.restype = C.c_int32
+    lib.apd_eval_register_sums.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p]
+    lib.apd_eval_register_sums_host.restype = C.c_int32
+    lib.apd_eval_register_sums_host.argtypes = [C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_float,
+                                                C.c_void_p]
+    lib.apd_eval_get_register_timing.restype = C.c_int32
+    lib.apd_eval_get_register_timing.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                                 C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_double),
+                                                 C.POINTER(C.c_double)]
     # include/apd_prep.h
     lib.apd_prep_create.restype = C.c_void_p
     lib.apd_prep_create.argtypes = [C.c_int32]
@@ -500,9 +544,102 @@ def cube_cameras(origin, size: int, lib: Optional[C.CDLL] = None):
     return [arr[i] for i in range(6)]
 
 
+def _mat4(T):
+    """None, or a contiguous float64 array of 16 (row-major 4x4)."""
+    if T is None:
+        return None
+    m = np.ascontiguousarray(T, np.float64).reshape(-1)
+    if m.size != 16:
+        raise ValueError("a transform is 4x4")
+    return m
+
+
+def _polygon(polygon):
+    poly = np.ascontiguousarray(polygon, np.float64)
+    if poly.ndim != 2 or poly.shape[1] != 2:
+        raise ValueError("a polygon is (m, 2) float64")
+    return poly, int(poly.shape[0])
+
+
+def _host_cloud(xyz):
+    a = np.ascontiguousarray(xyz, np.float32)
+    if a.ndim != 2 or a.shape[1] != 3:
+        raise ValueError(f"a cloud is (n, 3) float32, got shape {a.shape}")
+    return a, int(a.shape[0]), (a.ctypes.data if a.shape[0] else None)
+
+
+def _host_status(st: int, what: str, allow_state: bool = False):
+    if st != 0 and not (allow_state and STATUS.get(st) == "APD_ESTATE"):
+        raise ApdError(f"{what} -> {STATUS.get(st, st)}")
+
+
+def crop_volume_host(xyz, axis: int, axis_min: float, axis_max: float, polygon, T=None,
+                     lib: Optional[C.CDLL] = None) -> np.ndarray:
+    """apd_eval_crop_volume_host: the crop rule on one host thread. Needs no GPU."""
+    lib = lib or load_library()
+    a, n, addr = _host_cloud(xyz)
+    poly, m = _polygon(polygon)
+    Tm = _mat4(T)
+    keep = np.empty(max(n, 1), np.int32)
+    n_keep = C.c_int64(0)
+    _host_status(lib.apd_eval_crop_volume_host(n, addr, None if Tm is None else Tm.ctypes.data, int(axis),
+                                               float(axis_min), float(axis_max), m, poly.ctypes.data, keep.ctypes.data,
+                                               C.addressof(n_keep)), "apd_eval_crop_volume_host")
+    return keep[:n_keep.value].copy()
+
+
+def nearest_host(target, xyz, max_dist: float, lib: Optional[C.CDLL] = None):
+    """apd_eval_nearest_host: (dist, idx) of xyz against target. Needs no GPU."""
+    lib = lib or load_library()
+    t, nt, taddr = _host_cloud(target)
+    a, n, addr = _host_cloud(xyz)
+    dist, idx = np.empty(n, np.float32), np.empty(n, np.int32)
+    _host_status(lib.apd_eval_nearest_host(nt, taddr, n, addr, max_dist, dist.ctypes.data if n else None,
+                                           idx.ctypes.data if n else None), "apd_eval_nearest_host")
+    return dist, idx
+
+
+def transform_host(xyz, T=None, lib: Optional[C.CDLL] = None) -> np.ndarray:
+    lib = lib or load_library()
+    a, n, addr = _host_cloud(xyz)
+    Tm = _mat4(T)
+    out = np.empty((n, 3), np.float32)
+    _host_status(lib.apd_eval_transform_host(n, addr, None if Tm is None else Tm.ctypes.data,
+                                             out.ctypes.data if n else None), "apd_eval_transform_host")
+    return out
+
+
+def register_sums_host(target, xyz, max_corr: float, T=None, lib: Optional[C.CDLL] = None) -> np.ndarray:
+    lib = lib or load_library()
+    t, nt, taddr = _host_cloud(target)
+    a, n, addr = _host_cloud(xyz)
+    Tm = _mat4(T)
+    out = np.zeros(REG_SUMS, np.float64)
+    _host_status(lib.apd_eval_register_sums_host(nt, taddr, n, addr, None if Tm is None else Tm.ctypes.data, max_corr,
+                                                 out.ctypes.data), "apd_eval_register_sums_host")
+    return out
+
+
+def register_host(target, xyz, max_corr: float, T0=None, with_scale: bool = True, max_iter: int = 30,
+                  eps_fitness: float = 1e-6, eps_rmse: float = 1e-6, lib: Optional[C.CDLL] = None):
+    """apd_eval_register_host: (T float64[4, 4], info dict, status); APD_ESTATE is returned, not raised."""
+    lib = lib or load_library()
+    t, nt, taddr = _host_cloud(target)
+    a, n, addr = _host_cloud(xyz)
+    T0m = _mat4(T0)
+    T = np.zeros(16, np.float64)
+    info = ApdEvalRegInfo()
+    st = lib.apd_eval_register_host(nt, taddr, n, addr, None if T0m is None else T0m.ctypes.data, max_corr,
+                                    int(bool(with_scale)), int(max_iter), float(eps_fitness), float(eps_rmse),
+                                    T.ctypes.data, C.byref(info))
+    _host_status(st, "apd_eval_register_host", allow_state=True)
+    return T.reshape(4, 4), info.as_dict(), st
+
+
 class EvalEngine:
     """One apd_eval_ctx (include/apd_eval.h): truncated nearest-neighbour distances to a target cloud,
-    voxel down-sampling, z-buffer rendering and visibility, free gaps and voxel scores. Clouds are (n, 3) float32: numpy arrays (results come back as numpy) or
+    voxel down-sampling, z-buffer rendering and visibility, free gaps and voxel scores, crop volume,
+    nearest neighbour with index, transform and ICP registration. Clouds are (n, 3) float32: numpy arrays (results come back as numpy) or
     torch tensors on the context's device (results come back as tensors there; torch's current
     stream is waited for first, as for every device input of this library)."""
 
@@ -732,6 +869,94 @@ class EvalEngine:
         self._check(self.lib.apd_eval_get_protocol_timing(self.ctx, C.byref(f), C.byref(s)),
                     "apd_eval_get_protocol_timing")
         return {"free_gap_ms": f.value, "scores_ms": s.value}
+
+    # ---- crop volume, nearest neighbour with index, transform, registration ----
+
+    def crop_volume(self, xyz, axis: int, axis_min: float, axis_max: float, polygon, T=None):
+        """Ascending int32 indices of the points inside the crop volume (apd_eval_crop_volume)."""
+        a, n, addr, dev = self._cloud(xyz)
+        poly, m = _polygon(polygon)
+        Tm = _mat4(T)
+        if dev:
+            import torch
+            keep = torch.empty(max(n, 1), dtype=torch.int32, device=a.device)
+            _torch_device_sync(a, keep)
+            kptr = keep.data_ptr()
+        else:
+            keep = np.empty(max(n, 1), np.int32)
+            kptr = keep.ctypes.data
+        n_keep = C.c_int64(0)
+        self._check(self.lib.apd_eval_crop_volume(self.ctx, n, addr, None if Tm is None else Tm.ctypes.data, int(axis),
+                                                  float(axis_min), float(axis_max), m, poly.ctypes.data, kptr,
+                                                  C.addressof(n_keep)), "apd_eval_crop_volume")
+        return keep[:n_keep.value]
+
+    def nearest(self, xyz, max_dist: float):
+        """(dist float32[n], idx int32[n]): apd_eval_distances' values plus the lowest target index that
+        attains each, -1 where the distance is +inf."""
+        a, n, addr, dev = self._cloud(xyz)
+        if dev:
+            import torch
+            dist = torch.empty(n, dtype=torch.float32, device=a.device)
+            idx = torch.empty(n, dtype=torch.int32, device=a.device)
+            _torch_device_sync(a, dist, idx)
+            dptr, iptr = (dist.data_ptr(), idx.data_ptr()) if n else (None, None)
+        else:
+            dist, idx = np.empty(n, np.float32), np.empty(n, np.int32)
+            dptr, iptr = (dist.ctypes.data, idx.ctypes.data) if n else (None, None)
+        self._check(self.lib.apd_eval_nearest(self.ctx, n, addr, max_dist, dptr, iptr), "apd_eval_nearest")
+        return dist, idx
+
+    def transform(self, xyz, T=None):
+        """The cloud under the 4x4 double transform T, rounded to float32 (apd_eval_transform)."""
+        a, n, addr, dev = self._cloud(xyz)
+        Tm = _mat4(T)
+        if dev:
+            import torch
+            out = torch.empty((n, 3), dtype=torch.float32, device=a.device)
+            _torch_device_sync(a, out)
+            optr = out.data_ptr() if n else None
+        else:
+            out = np.empty((n, 3), np.float32)
+            optr = out.ctypes.data if n else None
+        self._check(self.lib.apd_eval_transform(self.ctx, n, addr, None if Tm is None else Tm.ctypes.data, optr),
+                    "apd_eval_transform")
+        return out
+
+    def register(self, xyz, max_corr: float, T0=None, with_scale: bool = True, max_iter: int = 30,
+                 eps_fitness: float = 1e-6, eps_rmse: float = 1e-6, raise_on_state: bool = True):
+        """Point-to-point ICP of xyz against the current target: (T float64[4, 4], info dict, status).
+        With raise_on_state False an APD_ESTATE outcome (fewer than 3 correspondences) is returned
+        instead of raised."""
+        a, n, addr, _ = self._cloud(xyz)
+        _torch_device_sync(a)
+        T0m = _mat4(T0)
+        T = np.zeros(16, np.float64)
+        info = ApdEvalRegInfo()
+        st = self.lib.apd_eval_register(self.ctx, n, addr, None if T0m is None else T0m.ctypes.data, max_corr,
+                                        int(bool(with_scale)), int(max_iter), float(eps_fitness), float(eps_rmse),
+                                        T.ctypes.data, C.byref(info))
+        if st != 0 and (raise_on_state or STATUS.get(st) != "APD_ESTATE"):
+            self._check(st, "apd_eval_register")
+        return T.reshape(4, 4), info.as_dict(), st
+
+    def register_sums(self, xyz, max_corr: float, T=None) -> np.ndarray:
+        """The 19 sums of one evaluation of T (include/apd_eval.h)."""
+        a, n, addr, _ = self._cloud(xyz)
+        _torch_device_sync(a)
+        Tm = _mat4(T)
+        out = np.zeros(REG_SUMS, np.float64)
+        self._check(self.lib.apd_eval_register_sums(self.ctx, n, addr, None if Tm is None else Tm.ctypes.data, max_corr,
+                                                    out.ctypes.data), "apd_eval_register_sums")
+        return out
+
+    def register_timing(self) -> dict:
+        e, f, s, c, t = C.c_double(), C.c_double(), C.c_double(), C.c_double(), C.c_double()
+        k = C.c_int32()
+        self._check(self.lib.apd_eval_get_register_timing(self.ctx, C.byref(e), C.byref(f), C.byref(s), C.byref(k),
+                                                          C.byref(c), C.byref(t)), "apd_eval_get_register_timing")
+        return {"eval_ms": e.value, "fold_ms": f.value, "solve_ms": s.value, "evaluations": k.value,
+                "crop_ms": c.value, "transform_ms": t.value}
 
     def close(self):
         if self.ctx:

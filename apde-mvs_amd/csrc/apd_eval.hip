@@ -1,7 +1,9 @@
 // apd_eval.hip — device side of the point-cloud evaluation (include/apd_eval.h): truncated
 // nearest-neighbour distances between two clouds, voxel down-sampling, and a z-buffer renderer of a
 // cloud into cameras with a per-point visibility count (integer atomics: deterministic), the
-// free-space gap of points against depth maps and per-voxel good / bad scores (integer sums).
+// free-space gap of points against depth maps and per-voxel good / bad scores (integer sums); a crop
+// volume, the nearest neighbour with its index, and point-to-point ICP whose per-iteration sums are
+// taken in a fixed tree order in fp64 (the same bits every run, and the host twins' bits).
 //
 // Search structure: a Morton-sorted implicit bounding-volume tree.
 //   - finite targets are quantised to 21 bits per axis over their bounding box (in double) and sorted
@@ -20,6 +22,7 @@
 #include <rocprim/iterator/counting_iterator.hpp>
 #include <rocprim/iterator/transform_iterator.hpp>
 
+#include <chrono>
 #include <cmath>
 #include <cstdint>
 #include <cstdlib>
@@ -29,6 +32,7 @@
 #include <vector>
 
 #include "../../include/apd_eval.h"
+#include "apd_register.h"
 
 namespace {
 
@@ -536,6 +540,201 @@ __global__ void __launch_bounds__(BLOCK) k_voxel_ratio(const uint64_t *__restric
     }
 }
 
+// ---- crop volume, nearest neighbour with index, registration ----------------------------------------
+
+struct Rows3 {
+    double m[12];  // rows 0..2 of a 4x4 transform
+};
+
+// The search of k_nearest with the index contract: the minimal computed d2 over the finite targets
+// (starting from bound_d2, see k_nearest), the lowest ORIGINAL index among the targets attaining it.
+// tidx maps a sorted position to the index given to set_target. best stays INT32_MAX when nothing is
+// within the bound; pos is the winner's sorted position. Equal d2 is never pruned (a node is skipped
+// only on box_d2 > cur), so every candidate for the tie is seen.
+__device__ __forceinline__ void offer_leaf(const Tree &T, const int *__restrict__ tidx, int leaf, float qx, float qy,
+                                           float qz, float &cur, int &best, int &pos) {
+    const int b = leaf * LEAF, e = min(b + LEAF, T.nf);
+    for (int j = b; j < e; ++j) {
+        const float d2 = point_d2(qx, qy, qz, T.pts[j]);
+        if (d2 <= cur) {
+            const int o = tidx[j];
+            if (d2 < cur || o < best) {
+                cur = d2;
+                best = o;
+                pos = j;
+            }
+        }
+    }
+}
+
+__device__ __forceinline__ void nn_search(const Tree &T, const int *__restrict__ tidx, uint64_t key, float qx, float qy,
+                                          float qz, float &cur, int &best, int &pos) {
+    int lo = 0, hi = T.nf;
+    while (lo < hi) {
+        const int mid = lo + ((hi - lo) >> 1);
+        if (T.keys[mid] < key) lo = mid + 1; else hi = mid;
+    }
+    const int leaf0 = min(lo, T.nf - 1) / LEAF;
+    offer_leaf(T, tidx, leaf0, qx, qy, qz, cur, best, pos);
+
+    uint32_t st_node[STACK];
+    float st_d2[STACK];
+    int sp = 0;
+    if (T.levels > 1) {
+        st_node[0] = (uint32_t)(T.levels - 1) << 27;
+        st_d2[0] = 0.0f;
+        sp = 1;
+    }
+    while (sp > 0) {
+        --sp;
+        if (st_d2[sp] > cur) continue;
+        const int lvl = (int)(st_node[sp] >> 27), idx = (int)(st_node[sp] & 0x7FFFFFFu);
+        const int cl = lvl - 1;
+        const int b = idx * FAN, e = min(b + FAN, T.cnt[cl]);
+        const float4 *cb = T.boxes + 2 * (size_t)T.off[cl];
+        for (int c = b; c < e; ++c) {
+            const float bd = box_d2(qx, qy, qz, cb[2 * (size_t)c], cb[2 * (size_t)c + 1]);
+            if (bd > cur) continue;
+            if (cl == 0) {
+                if (c != leaf0) offer_leaf(T, tidx, c, qx, qy, qz, cur, best, pos);
+            } else if (sp < STACK) {  // always true (see STACK)
+                st_node[sp] = (uint32_t)cl << 27 | (uint32_t)c;
+                st_d2[sp] = bd;
+                ++sp;
+            }
+        }
+    }
+}
+
+// k_nearest with idx: one lane per query, queries in Morton order. dist and idx may be nullptr.
+__global__ void __launch_bounds__(BLOCK) k_nearest_idx(const Tree T, const int *__restrict__ tidx, int nq,
+                                                       const uint64_t *__restrict__ qkeys,
+                                                       const int *__restrict__ qidx, const float *__restrict__ qxyz,
+                                                       float bound_d2, float max_dist, float *__restrict__ dist,
+                                                       int *__restrict__ idx) {
+    const int i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= nq) return;
+    const int qi = qidx[i];
+    const uint64_t key = qkeys[i];
+    float r = __uint_as_float(0x7F800000u);
+    int ri = -1;
+    if (key != KEY_NONE && T.nf > 0) {
+        const float qx = qxyz[3 * (size_t)qi], qy = qxyz[3 * (size_t)qi + 1], qz = qxyz[3 * (size_t)qi + 2];
+        float cur = bound_d2;
+        int best = INT32_MAX, pos = 0;
+        nn_search(T, tidx, key, qx, qy, qz, cur, best, pos);
+        if (best != INT32_MAX) {
+            const float m = sqrtf(cur);
+            if (m <= max_dist) {
+                r = m;
+                ri = best;
+            }
+        }
+    }
+    if (dist) dist[qi] = r;
+    if (idx) idx[qi] = ri;
+}
+
+// One evaluation of a transform, fused: transform, search and the block's tree sum; no q array is
+// written. A workgroup of BLOCK lanes owns APD_REG_BLOCK = 4 * BLOCK consecutive source indices and
+// takes them in four passes of one index per lane. Per pass the 19 fp64 terms are summed over the
+// wave by a butterfly (xor 1, 2, .. 32: IEEE addition commutes, so every lane holds the balanced
+// tree's sum over the wave's 64 consecutive indices); lane 0 parks it in LDS slot 4 * pass + wave,
+// i.e. in index order. The 16 slots are then summed by the same balanced tree, which makes the whole
+// the balanced binary tree over the block's 1024 indices. Indices >= n contribute +0.0 terms.
+// Every lane runs every pass to the end: the shuffles need the whole wave.
+constexpr int REG_SLOTS = APD_REG_BLOCK / 64;
+static_assert(APD_REG_BLOCK == 4 * BLOCK && REG_SLOTS == 16, "the tree below is written for 16 wave sums");
+__global__ void __launch_bounds__(BLOCK) k_reg_eval(const Tree T, const int *__restrict__ tidx,
+                                                    const uint32_t *__restrict__ bounds,
+                                                    const float *__restrict__ xyz, int n, const Rows3 M, float bound_d2,
+                                                    float max_corr, double *__restrict__ partials) {
+    __shared__ double slot[REG_SLOTS][APD_REG_SUMS];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int pass = 0; pass < APD_REG_BLOCK / BLOCK; ++pass) {
+        const int64_t i = (int64_t)blockIdx.x * APD_REG_BLOCK + pass * BLOCK + threadIdx.x;
+        float qx = 0.0f, qy = 0.0f, qz = 0.0f, tx = 0.0f, ty = 0.0f, tz = 0.0f, d2 = 0.0f;
+        bool fin = false, has = false;
+        if (i < n) {
+            double p[3];
+            apd_reg_xform(M.m, xyz[3 * (size_t)i], xyz[3 * (size_t)i + 1], xyz[3 * (size_t)i + 2], p);
+            qx = (float)p[0];
+            qy = (float)p[1];
+            qz = (float)p[2];
+            fin = finite3(qx, qy, qz);
+            if (fin && T.nf > 0) {
+                const uint64_t key = spread21(quant21(qx, bounds[0], bounds[3])) << 2 |
+                                     spread21(quant21(qy, bounds[1], bounds[4])) << 1 |
+                                     spread21(quant21(qz, bounds[2], bounds[5]));
+                float cur = bound_d2;
+                int best = INT32_MAX, pos = 0;
+                nn_search(T, tidx, key, qx, qy, qz, cur, best, pos);
+                if (best != INT32_MAX && sqrtf(cur) <= max_corr) {
+                    const float4 t = T.pts[pos];
+                    has = true;
+                    tx = t.x;
+                    ty = t.y;
+                    tz = t.z;
+                    d2 = cur;
+                }
+            }
+        }
+        double v[APD_REG_SUMS];
+        apd_reg_terms(fin, has, qx, qy, qz, tx, ty, tz, d2, v);
+        for (int k = 0; k < APD_REG_SUMS; ++k) {
+            double a = v[k];
+            for (int s = 1; s < 64; s <<= 1) a += __shfl_xor(a, s);
+            if (lane == 0) slot[pass * (BLOCK / 64) + wave][k] = a;
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x < APD_REG_SUMS) {
+        double a[REG_SLOTS];
+        for (int w = 0; w < REG_SLOTS; ++w) a[w] = slot[w][threadIdx.x];
+        for (int w = REG_SLOTS; w > 1; w >>= 1)
+            for (int j = 0; j < w / 2; ++j) a[j] = a[2 * j] + a[2 * j + 1];
+        partials[(size_t)blockIdx.x * APD_REG_SUMS + threadIdx.x] = a[0];
+    }
+}
+
+// The block sums left to right in block order, one lane per sum; no block: +0.0.
+__global__ void __launch_bounds__(64) k_reg_fold(const double *__restrict__ partials, int nblocks, double *out) {
+    if (threadIdx.x >= APD_REG_SUMS) return;
+    double s = 0.0;
+    if (nblocks > 0) s = partials[threadIdx.x];
+    // the additions are a serial chain; the loads are not, so they are issued eight blocks ahead
+    int b = 1;
+    for (; b + 8 <= nblocks; b += 8) {
+        double v[8];
+        for (int k = 0; k < 8; ++k) v[k] = partials[(size_t)(b + k) * APD_REG_SUMS + threadIdx.x];
+        for (int k = 0; k < 8; ++k) s += v[k];
+    }
+    for (; b < nblocks; ++b) s += partials[(size_t)b * APD_REG_SUMS + threadIdx.x];
+    out[threadIdx.x] = s;
+}
+
+// One lane per point: the crop rule; the polygon is read from memory at wave-uniform addresses.
+__global__ void __launch_bounds__(BLOCK) k_crop_flags(const float *__restrict__ xyz, int n, const Rows3 M, int has_T,
+                                                      int axis, double axis_min, double axis_max, int m,
+                                                      const double *__restrict__ poly, int *flag) {
+    const int i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= n) return;
+    flag[i] = apd_reg_crop_keep(has_T ? M.m : nullptr, axis, axis_min, axis_max, m, poly, xyz[3 * (size_t)i],
+                                xyz[3 * (size_t)i + 1], xyz[3 * (size_t)i + 2])
+                  ? 1
+                  : 0;
+}
+
+__global__ void __launch_bounds__(BLOCK) k_transform(const float *__restrict__ xyz, int n, const Rows3 M, float *out) {
+    const int i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= n) return;
+    double p[3];
+    apd_reg_xform(M.m, xyz[3 * (size_t)i], xyz[3 * (size_t)i + 1], xyz[3 * (size_t)i + 2], p);
+    out[3 * (size_t)i] = (float)p[0];
+    out[3 * (size_t)i + 1] = (float)p[1];
+    out[3 * (size_t)i + 2] = (float)p[2];
+}
+
 struct Buf {
     void *p = nullptr;
     size_t bytes = 0;
@@ -568,6 +767,12 @@ struct apd_eval_ctx {
     // the four sums of every tolerance
     Buf s_dist, s_gap, s_cnt, s_out;
     double free_gap_ms = 0.0, scores_ms = 0.0;
+    // crop / nearest with index / transform / registration: the polygon, the transformed cloud, the
+    // per-block sums and the 19 folded sums; a third event splits the evaluation from the fold
+    Buf c_poly, x_out, g_part, g_sums, n_idx;
+    hipEvent_t ev2 = nullptr;
+    double reg_eval_ms = 0.0, reg_fold_ms = 0.0, reg_solve_ms = 0.0, crop_ms = 0.0, transform_ms = 0.0;
+    int reg_evaluations = 0;
 };
 
 #define EV_OK(ctx, call)                                                                           \
@@ -688,7 +893,8 @@ apd_eval_ctx *apd_eval_create(int32_t device) {
     ctx->device = device;
     if (const char *e = getenv("APD_EVAL_RENDER_ORDER")) ctx->render_morton = strcmp(e, "morton") == 0;
     if (hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking) != hipSuccess ||
-        hipEventCreate(&ctx->ev0) != hipSuccess || hipEventCreate(&ctx->ev1) != hipSuccess) {
+        hipEventCreate(&ctx->ev0) != hipSuccess || hipEventCreate(&ctx->ev1) != hipSuccess ||
+        hipEventCreate(&ctx->ev2) != hipSuccess) {
         apd_eval_destroy(ctx);
         return nullptr;
     }
@@ -701,10 +907,12 @@ void apd_eval_destroy(apd_eval_ctx *ctx) {
     for (Buf *b : {&ctx->t_xyz, &ctx->t_keys, &ctx->t_keys_s, &ctx->t_idx, &ctx->t_idx_s, &ctx->t_pts, &ctx->t_boxes,
                    &ctx->q_xyz, &ctx->q_keys, &ctx->q_keys_s, &ctx->q_idx, &ctx->q_idx_s, &ctx->q_dist, &ctx->q_aux,
                    &ctx->sort_tmp, &ctx->small, &ctx->r_keys, &ctx->r_depth, &ctx->r_index, &ctx->r_small, &ctx->s_dist,
-                   &ctx->s_gap, &ctx->s_cnt, &ctx->s_out})
+                   &ctx->s_gap, &ctx->s_cnt, &ctx->s_out, &ctx->c_poly, &ctx->x_out, &ctx->g_part, &ctx->g_sums,
+                   &ctx->n_idx})
         if (b->p) (void)hipFree(b->p);
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
     if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
+    if (ctx->ev2) (void)hipEventDestroy(ctx->ev2);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
 }
@@ -1260,6 +1468,256 @@ int32_t apd_eval_get_protocol_timing(apd_eval_ctx *ctx, double *free_gap_ms, dou
     if (!ctx) return APD_EINVAL;
     if (free_gap_ms) *free_gap_ms = ctx->free_gap_ms;
     if (scores_ms) *scores_ms = ctx->scores_ms;
+    return APD_OK;
+}
+
+// ---- crop volume, nearest neighbour with index, transform, registration ---------------------------
+
+static bool finite16(const double *T) {
+    if (!T) return true;
+    for (int i = 0; i < 16; ++i)
+        if (!std::isfinite(T[i])) return false;
+    return true;
+}
+
+static Rows3 rows_of(const double *T) {
+    Rows3 M;
+    for (int i = 0; i < 12; ++i) M.m[i] = T ? T[i] : (i % 5 == 0 ? 1.0 : 0.0);
+    return M;
+}
+
+int32_t apd_eval_crop_volume(apd_eval_ctx *ctx, int64_t n64, const float *xyz, const double *T, int32_t axis,
+                             double axis_min, double axis_max, int32_t m, const double *poly, int32_t *keep_idx,
+                             int64_t *n_keep) {
+    if (!ctx) return APD_EINVAL;
+    int st = check_n(ctx, "apd_eval_crop_volume", n64, xyz);
+    if (st) return st;
+    if (!n_keep || (n64 > 0 && !keep_idx) || !poly) {
+        ctx->err = "apd_eval_crop_volume: NULL polygon or output";
+        return APD_EINVAL;
+    }
+    if (m < 3 || m > (1 << 20) || axis < 0 || axis > 2 || !std::isfinite(axis_min) || !std::isfinite(axis_max) ||
+        !finite16(T)) {
+        ctx->err = "apd_eval_crop_volume: fewer than 3 or more than 2^20 vertices, a bad axis, or a non-finite bound or "
+                   "transform";
+        return APD_EINVAL;
+    }
+    for (int i = 0; i < 2 * m; ++i)
+        if (!std::isfinite(poly[i])) {
+            ctx->err = "apd_eval_crop_volume: a non-finite polygon vertex";
+            return APD_EINVAL;
+        }
+    EV_OK(ctx, hipSetDevice(ctx->device));
+    const int n = (int)n64;
+    ctx->crop_ms = 0.0;
+    unsigned long long kept = 0;
+    if (n == 0) {
+        EV_OK(ctx, hipMemcpy(n_keep, &kept, 8, hipMemcpyDefault));
+        return APD_OK;
+    }
+    // q_dist holds the flags, q_aux their exclusive scan from byte 128 and the kept count at byte 64,
+    // q_keys the kept indices (the layout of apd_eval_voxel_downsample)
+    if ((st = grow(ctx, ctx->q_xyz, (size_t)n * 12)) || (st = grow(ctx, ctx->q_keys, (size_t)n * 8)) ||
+        (st = grow(ctx, ctx->q_dist, (size_t)n * 4)) || (st = grow(ctx, ctx->q_aux, 128 + (size_t)n * 4)) ||
+        (st = grow(ctx, ctx->c_poly, (size_t)m * 16)))
+        return st;
+    unsigned long long *counter = (unsigned long long *)((char *)ctx->q_aux.p + 64);
+    int *flag = (int *)ctx->q_dist.p, *pos = (int *)ctx->q_aux.p + 32, *keep = (int *)ctx->q_keys.p;
+    hipStream_t s = ctx->stream;
+    EV_OK(ctx, hipMemcpyAsync(ctx->q_xyz.p, xyz, (size_t)n * 12, hipMemcpyDefault, s));
+    EV_OK(ctx, hipMemcpyAsync(ctx->c_poly.p, poly, (size_t)m * 16, hipMemcpyHostToDevice, s));
+    EV_OK(ctx, hipEventRecord(ctx->ev0, s));
+    hipLaunchKernelGGL(k_crop_flags, dim3(grid_for(n)), dim3(BLOCK), 0, s, (const float *)ctx->q_xyz.p, n, rows_of(T),
+                       T ? 1 : 0, (int)axis, axis_min, axis_max, (int)m, (const double *)ctx->c_poly.p, flag);
+    EV_OK(ctx, hipGetLastError());
+    size_t tb = 0;
+    EV_OK(ctx, rocprim::exclusive_scan(nullptr, tb, flag, pos, 0, (size_t)n, rocprim::plus<int>(), s));
+    if ((st = grow(ctx, ctx->sort_tmp, tb))) return st;
+    EV_OK(ctx, rocprim::exclusive_scan(ctx->sort_tmp.p, tb, flag, pos, 0, (size_t)n, rocprim::plus<int>(), s));
+    hipLaunchKernelGGL(k_voxel_compact, dim3(grid_for(n)), dim3(BLOCK), 0, s, (const int *)flag, (const int *)pos, n,
+                       keep, counter);
+    EV_OK(ctx, hipGetLastError());
+    EV_OK(ctx, hipEventRecord(ctx->ev1, s));
+    EV_OK(ctx, hipMemcpyAsync(&kept, counter, 8, hipMemcpyDeviceToHost, s));
+    EV_OK(ctx, hipStreamSynchronize(s));  // the polygon has been read: the caller's array is free again
+    if (kept > 0) EV_OK(ctx, hipMemcpy(keep_idx, keep, (size_t)kept * 4, hipMemcpyDefault));
+    EV_OK(ctx, hipMemcpy(n_keep, &kept, 8, hipMemcpyDefault));
+    return elapsed(ctx, ctx->crop_ms);
+}
+
+int32_t apd_eval_nearest(apd_eval_ctx *ctx, int64_t n64, const float *xyz, float max_dist, float *dist, int32_t *idx) {
+    if (!ctx) return APD_EINVAL;
+    int st = check_n(ctx, "apd_eval_nearest", n64, xyz);
+    if (st) return st;
+    if (!(max_dist >= 0.0f)) {
+        ctx->err = "apd_eval_nearest: max_dist is negative or NaN";
+        return APD_EINVAL;
+    }
+    if (!ctx->has_target) {
+        ctx->err = "apd_eval_nearest: no target set";
+        return APD_ESTATE;
+    }
+    const int n = (int)n64;
+    ctx->query_ms = 0.0;
+    if (n == 0) return APD_OK;
+    EV_OK(ctx, hipSetDevice(ctx->device));
+    if ((st = grow(ctx, ctx->q_xyz, (size_t)n * 12)) || (st = grow(ctx, ctx->q_keys, (size_t)n * 8)) ||
+        (st = grow(ctx, ctx->q_keys_s, (size_t)n * 8)) || (st = grow(ctx, ctx->q_idx, (size_t)n * 4)) ||
+        (st = grow(ctx, ctx->q_idx_s, (size_t)n * 4)) || (st = grow(ctx, ctx->q_dist, (size_t)n * 4)) ||
+        (st = grow(ctx, ctx->n_idx, (size_t)n * 4)) || (st = grow(ctx, ctx->small, 256)))
+        return st;
+    hipStream_t s = ctx->stream;
+    EV_OK(ctx, hipMemcpyAsync(ctx->q_xyz.p, xyz, (size_t)n * 12, hipMemcpyDefault, s));
+    EV_OK(ctx, hipEventRecord(ctx->ev0, s));
+    const uint32_t *bounds = (const uint32_t *)ctx->small.p;  // the target's box, as in apd_eval_distances
+    hipLaunchKernelGGL(k_morton_keys, dim3(grid_for(n)), dim3(BLOCK), 0, s, (const float *)ctx->q_xyz.p, n, bounds,
+                       (uint64_t *)ctx->q_keys.p, (int *)ctx->q_idx.p, (unsigned long long *)nullptr);
+    EV_OK(ctx, hipGetLastError());
+    if ((st = sort_pairs(ctx, ctx->q_keys, ctx->q_keys_s, ctx->q_idx, ctx->q_idx_s, n))) return st;
+    hipLaunchKernelGGL(k_nearest_idx, dim3(grid_for(n)), dim3(BLOCK), 0, s, ctx->tree, (const int *)ctx->t_idx_s.p, n,
+                       (const uint64_t *)ctx->q_keys_s.p, (const int *)ctx->q_idx_s.p, (const float *)ctx->q_xyz.p,
+                       d2_bound(max_dist), max_dist, (float *)ctx->q_dist.p, (int *)ctx->n_idx.p);
+    EV_OK(ctx, hipGetLastError());
+    EV_OK(ctx, hipEventRecord(ctx->ev1, s));
+    if (dist) EV_OK(ctx, hipMemcpyAsync(dist, ctx->q_dist.p, (size_t)n * 4, hipMemcpyDefault, s));
+    if (idx) EV_OK(ctx, hipMemcpyAsync(idx, ctx->n_idx.p, (size_t)n * 4, hipMemcpyDefault, s));
+    EV_OK(ctx, hipStreamSynchronize(s));
+    return elapsed(ctx, ctx->query_ms);
+}
+
+int32_t apd_eval_transform(apd_eval_ctx *ctx, int64_t n64, const float *xyz, const double *T, float *out) {
+    if (!ctx) return APD_EINVAL;
+    int st = check_n(ctx, "apd_eval_transform", n64, xyz);
+    if (st) return st;
+    if ((n64 > 0 && !out) || !finite16(T)) {
+        ctx->err = "apd_eval_transform: NULL output or a non-finite transform";
+        return APD_EINVAL;
+    }
+    const int n = (int)n64;
+    ctx->transform_ms = 0.0;
+    if (n == 0) return APD_OK;
+    EV_OK(ctx, hipSetDevice(ctx->device));
+    if ((st = grow(ctx, ctx->q_xyz, (size_t)n * 12)) || (st = grow(ctx, ctx->x_out, (size_t)n * 12))) return st;
+    hipStream_t s = ctx->stream;
+    EV_OK(ctx, hipMemcpyAsync(ctx->q_xyz.p, xyz, (size_t)n * 12, hipMemcpyDefault, s));
+    EV_OK(ctx, hipEventRecord(ctx->ev0, s));
+    hipLaunchKernelGGL(k_transform, dim3(grid_for(n)), dim3(BLOCK), 0, s, (const float *)ctx->q_xyz.p, n, rows_of(T),
+                       (float *)ctx->x_out.p);
+    EV_OK(ctx, hipGetLastError());
+    EV_OK(ctx, hipEventRecord(ctx->ev1, s));
+    EV_OK(ctx, hipMemcpyAsync(out, ctx->x_out.p, (size_t)n * 12, hipMemcpyDefault, s));
+    EV_OK(ctx, hipStreamSynchronize(s));
+    return elapsed(ctx, ctx->transform_ms);
+}
+
+// uploads the source once; reg_sums then evaluates a transform: the fused kernel, the fold, 19 doubles back
+static int reg_upload(apd_eval_ctx *ctx, int n, const float *xyz) {
+    int st;
+    const int nblocks = (n + APD_REG_BLOCK - 1) / APD_REG_BLOCK;
+    if ((st = grow(ctx, ctx->q_xyz, (size_t)std::max(n, 1) * 12)) ||
+        (st = grow(ctx, ctx->g_part, (size_t)std::max(nblocks, 1) * APD_REG_SUMS * 8)) ||
+        (st = grow(ctx, ctx->g_sums, APD_REG_SUMS * 8)) || (st = grow(ctx, ctx->small, 256)))
+        return st;
+    if (n > 0) EV_OK(ctx, hipMemcpyAsync(ctx->q_xyz.p, xyz, (size_t)n * 12, hipMemcpyDefault, ctx->stream));
+    ctx->reg_eval_ms = ctx->reg_fold_ms = ctx->reg_solve_ms = 0.0;
+    ctx->reg_evaluations = 0;
+    return APD_OK;
+}
+
+static int reg_sums(apd_eval_ctx *ctx, int n, const double *T, float max_corr, float bound_d2, double *m) {
+    hipStream_t s = ctx->stream;
+    const int nblocks = (n + APD_REG_BLOCK - 1) / APD_REG_BLOCK;
+    EV_OK(ctx, hipEventRecord(ctx->ev0, s));
+    if (nblocks > 0)
+        hipLaunchKernelGGL(k_reg_eval, dim3(nblocks), dim3(BLOCK), 0, s, ctx->tree, (const int *)ctx->t_idx_s.p,
+                           (const uint32_t *)ctx->small.p, (const float *)ctx->q_xyz.p, n, rows_of(T), bound_d2, max_corr,
+                           (double *)ctx->g_part.p);
+    EV_OK(ctx, hipEventRecord(ctx->ev1, s));
+    hipLaunchKernelGGL(k_reg_fold, dim3(1), dim3(64), 0, s, (const double *)ctx->g_part.p, nblocks,
+                       (double *)ctx->g_sums.p);
+    EV_OK(ctx, hipGetLastError());
+    EV_OK(ctx, hipEventRecord(ctx->ev2, s));
+    EV_OK(ctx, hipMemcpyAsync(m, ctx->g_sums.p, APD_REG_SUMS * 8, hipMemcpyDeviceToHost, s));
+    EV_OK(ctx, hipStreamSynchronize(s));
+    float a = 0.0f, b = 0.0f;
+    EV_OK(ctx, hipEventElapsedTime(&a, ctx->ev0, ctx->ev1));
+    EV_OK(ctx, hipEventElapsedTime(&b, ctx->ev1, ctx->ev2));
+    ctx->reg_eval_ms += (double)a;
+    ctx->reg_fold_ms += (double)b;
+    ++ctx->reg_evaluations;
+    return APD_OK;
+}
+
+static int reg_check(apd_eval_ctx *ctx, const char *what, int64_t n, const float *xyz, const double *T0,
+                     float max_corr) {
+    int st = check_n(ctx, what, n, xyz);
+    if (st) return st;
+    if (!finite16(T0) || !(max_corr > 0.0f) || !std::isfinite(max_corr)) {
+        ctx->err = std::string(what) + ": a non-finite transform, or max_corr not positive and finite";
+        return APD_EINVAL;
+    }
+    if (!ctx->has_target) {
+        ctx->err = std::string(what) + ": no target set";
+        return APD_ESTATE;
+    }
+    return APD_OK;
+}
+
+int32_t apd_eval_register_sums(apd_eval_ctx *ctx, int64_t n64, const float *xyz, const double *T, float max_corr,
+                               double *sums) {
+    if (!ctx) return APD_EINVAL;
+    int st = reg_check(ctx, "apd_eval_register_sums", n64, xyz, T, max_corr);
+    if (st) return st;
+    if (!sums) {
+        ctx->err = "apd_eval_register_sums: NULL output";
+        return APD_EINVAL;
+    }
+    EV_OK(ctx, hipSetDevice(ctx->device));
+    if ((st = reg_upload(ctx, (int)n64, xyz))) return st;
+    return reg_sums(ctx, (int)n64, T, max_corr, d2_bound(max_corr), sums);
+}
+
+int32_t apd_eval_register(apd_eval_ctx *ctx, int64_t n64, const float *xyz, const double *T0, float max_corr,
+                          int32_t with_scale, int32_t max_iter, double eps_fitness, double eps_rmse, double *T,
+                          apd_eval_reg_info *info) {
+    if (!ctx) return APD_EINVAL;
+    int st = reg_check(ctx, "apd_eval_register", n64, xyz, T0, max_corr);
+    if (st) return st;
+    if (!T || !info || with_scale < 0 || with_scale > 1 || max_iter < 1 || max_iter > 1000 || !(eps_fitness >= 0.0) ||
+        !(eps_rmse >= 0.0)) {
+        ctx->err = "apd_eval_register: NULL output, with_scale outside 0..1, max_iter outside 1..1000 or a bad eps";
+        return APD_EINVAL;
+    }
+    EV_OK(ctx, hipSetDevice(ctx->device));
+    const int n = (int)n64;
+    if ((st = reg_upload(ctx, n, xyz))) return st;
+    const float bound = d2_bound(max_corr);
+    // host time of the solves: the loop's wall time minus what it spent waiting on the evaluations
+    using clk = std::chrono::steady_clock;
+    std::chrono::duration<double, std::milli> waited{0.0};
+    const clk::time_point t0 = clk::now();
+    st = apd_reg_iterate(T0, with_scale, max_iter, eps_fitness, eps_rmse, T, info, [&](const double *cur, double *m) {
+        const clk::time_point a = clk::now();
+        const int r = reg_sums(ctx, n, cur, max_corr, bound, m);
+        waited += clk::now() - a;
+        return (int32_t)r;
+    });
+    const std::chrono::duration<double, std::milli> total = clk::now() - t0;
+    ctx->reg_solve_ms = std::max(0.0, (total - waited).count());
+    if (st == APD_ESTATE)
+        ctx->err = "apd_eval_register: fewer than 3 correspondences or a degenerate configuration";
+    return st;
+}
+
+int32_t apd_eval_get_register_timing(apd_eval_ctx *ctx, double *eval_ms, double *fold_ms, double *solve_ms,
+                                     int32_t *evaluations, double *crop_ms, double *transform_ms) {
+    if (!ctx) return APD_EINVAL;
+    if (eval_ms) *eval_ms = ctx->reg_eval_ms;
+    if (fold_ms) *fold_ms = ctx->reg_fold_ms;
+    if (solve_ms) *solve_ms = ctx->reg_solve_ms;
+    if (evaluations) *evaluations = ctx->reg_evaluations;
+    if (crop_ms) *crop_ms = ctx->crop_ms;
+    if (transform_ms) *transform_ms = ctx->transform_ms;
     return APD_OK;
 }
 

@@ -7,6 +7,9 @@
 // restrict completeness to the ground-truth points such a z-buffer test sees (--visible_views).
 // Scanner mode (--gt_mlp) reads the MeshLab project of the laser scans and scores with a scanner
 // free-space test and voxel averages, modelled on the ETH3D protocol (not the ETH3D tool itself).
+// Tanks and Temples mode (--tat_gt) moves the reconstruction into the scan's frame, refines that by ICP
+// on the GPU, cuts both clouds to the scene's crop volume, thins both by voxel and reports precision,
+// recall and F-score at tau (modelled on the Tanks and Temples toolbox, not that toolbox).
 #include <algorithm>
 #include <atomic>
 #include <cmath>
@@ -88,6 +91,26 @@ const char *kHelp =
     "  Parity with that tool is unpinned; the numbers are not for published tables.\n"
     "  --gt_mlp excludes --gt, --dense_folder, --render_gt, --visible_views and --scan.\n"
     "\n"
+    "Tanks and Temples mode (uses the GPU):\n"
+    "  apd_eval --cloud REC.ply --tat_gt SCENE.ply --tat_crop SCENE.json --tau T [--tat_trans SCENE_trans.txt]\n"
+    "           [--init_trans FILE] [--no_refine] [--refine_stages v:c,v:c,...] [--no_scale]\n"
+    "           [--aligned_cloud_out OUT.ply] [--gpu_index G] [--json OUT.json]\n"
+    "  SCENE.ply is the laser scan, SCENE.json its crop volume (Open3D SelectionPolygonVolume: axis_min,\n"
+    "  axis_max, orthogonal_axis, bounding_polygon), the matrices are 4x4 text files mapping the\n"
+    "  reconstruction's frame to the scan's (default identity; --init_trans is applied after --tat_trans).\n"
+    "  1. T = init * trans. 2. Unless --no_refine, T is refined by point-to-point ICP with scaling\n"
+    "  (--no_scale: rigid) in stages (voxel:max_corr, default T:80T, T/2:20T, T/2:2T): per stage both\n"
+    "  clouds are cut to the crop volume (the reconstruction under T) and voxel-downsampled (the\n"
+    "  reconstruction in the scan's frame; the lowest-index point of a voxel represents it), then 20\n"
+    "  iterations at the most. 3. Both clouds are cropped with the final T and downsampled at T/2.\n"
+    "  4. precision = share of reconstruction points closer than T to the scan, recall the same share the\n"
+    "  other way, fscore = 2PR / (P + R). --aligned_cloud_out writes all of REC.ply under the final T.\n"
+    "  Modelled on the Tanks and Temples toolbox, NOT that toolbox: a voxel is represented by its\n"
+    "  lowest-index point, not its mean; the third stage downsamples by voxel, not uniformly; there is no\n"
+    "  alignment from camera trajectories (.log). Parity is unpinned. --tat_dump prints what the readers\n"
+    "  understood of --tat_crop / --tat_trans / --init_trans and exits.\n"
+    "  --tat_gt excludes every other mode.\n"
+    "\n"
     "The modes may be combined in one invocation; --json then holds all of them.\n"
     "Exit status: 0 ok, 1 run-time failure, 2 bad arguments or unreadable input.\n";
 
@@ -103,6 +126,11 @@ struct Options {
     float max_dist = -1.0f;  // < 0: the largest tolerance
     float voxel = 0.0f;
     int gpu = 0;
+    // Tanks and Temples mode
+    std::string tat_gt, tat_crop, tat_trans, init_trans, aligned_out;
+    float tau = 0.0f;
+    bool tau_given = false, no_refine = false, no_scale = false, tat_dump = false, stages_given = false;
+    std::vector<std::pair<float, float>> stages;  // (voxel, max_corr)
 };
 
 bool parse_float(const std::string &s, float &v) {
@@ -652,6 +680,241 @@ int run_scanners(const Options &opt, ScannerInputs &in, std::string &json) {
     return 0;
 }
 
+// ---- Tanks and Temples mode ------------------------------------------------------------------------
+
+struct TatInputs {
+    std::vector<float> rec, gt;
+    TatCrop crop;
+    double trans[16], init[16];
+};
+
+void identity16(double *M) {
+    for (int i = 0; i < 16; ++i) M[i] = i % 5 == 0 ? 1.0 : 0.0;
+}
+
+void mul16(const double *A, const double *B, double *C) {
+    double r[16];
+    for (int i = 0; i < 4; ++i)
+        for (int j = 0; j < 4; ++j) {
+            double s = 0.0;
+            for (int k = 0; k < 4; ++k) s += A[4 * i + k] * B[4 * k + j];
+            r[4 * i + j] = s;
+        }
+    std::copy(r, r + 16, C);
+}
+
+std::string json_mat(const double *M) {
+    std::string s = "[";
+    for (int i = 0; i < 16; ++i) s += (i ? ", " : "") + fmt_g(M[i]);
+    return s + "]";
+}
+
+std::vector<float> gather(const std::vector<float> &xyz, const std::vector<int32_t> &keep, int64_t nk) {
+    std::vector<float> out((size_t)nk * 3);
+    for (int64_t i = 0; i < nk; ++i)
+        for (int a = 0; a < 3; ++a) out[3 * (size_t)i + a] = xyz[3 * (size_t)keep[(size_t)i] + a];
+    return out;
+}
+
+struct TatStage {
+    float voxel = 0.0f, max_corr = 0.0f;
+    int64_t source_points = 0, target_points = 0;
+    apd_eval_reg_info info{};
+    bool ok = false;
+    double eval_ms = 0.0, fold_ms = 0.0, solve_ms = 0.0;
+    int32_t evaluations = 0;
+};
+
+// returns the exit status; appends "tat": {...} to json
+int run_tat(const Options &opt, const TatInputs &in, std::string &json) {
+    apd_eval_ctx *ctx = apd_eval_create(opt.gpu);
+    if (!ctx) {
+        std::fprintf(stderr, "apd_eval: %s (device %d)\n", apd_eval_last_error(nullptr), opt.gpu);
+        return 1;
+    }
+    const std::vector<double> poly = in.crop.polygon();
+    const int32_t m = (int32_t)(poly.size() / 2);
+    double crop_ms = 0.0, voxel_ms = 0.0, transform_ms = 0.0;
+    bool ok = true;
+    auto crop = [&](const std::vector<float> &xyz, const double *T, std::vector<float> &out) {
+        const int64_t n = (int64_t)(xyz.size() / 3);
+        std::vector<int32_t> keep((size_t)std::max<int64_t>(n, 1));
+        int64_t nk = 0;
+        const int st = apd_eval_crop_volume(ctx, n, xyz.data(), T, in.crop.axis, in.crop.axis_min, in.crop.axis_max, m,
+                                            poly.data(), keep.data(), &nk);
+        if (st != APD_OK) return fail_ctx(ctx, "apd_eval_crop_volume", st);
+        double ms = 0.0;
+        apd_eval_get_register_timing(ctx, nullptr, nullptr, nullptr, nullptr, &ms, nullptr);
+        crop_ms += ms;
+        out = gather(xyz, keep, nk);
+        return true;
+    };
+    auto transform = [&](const std::vector<float> &xyz, const double *T, std::vector<float> &out) {
+        out.resize(xyz.size());
+        const int st = apd_eval_transform(ctx, (int64_t)(xyz.size() / 3), xyz.data(), T, out.data());
+        if (st != APD_OK) return fail_ctx(ctx, "apd_eval_transform", st);
+        double ms = 0.0;
+        apd_eval_get_register_timing(ctx, nullptr, nullptr, nullptr, nullptr, nullptr, &ms);
+        transform_ms += ms;
+        return true;
+    };
+    // indices of the lowest-index point of every voxel of `at` (the cloud in the scan's frame)
+    auto voxel_keep = [&](const std::vector<float> &at, float voxel, std::vector<int32_t> &keep, int64_t &nk) {
+        const int64_t n = (int64_t)(at.size() / 3);
+        keep.assign((size_t)std::max<int64_t>(n, 1), 0);
+        const int st = apd_eval_voxel_downsample(ctx, n, at.data(), voxel, keep.data(), &nk);
+        if (st != APD_OK) return fail_ctx(ctx, "apd_eval_voxel_downsample", st);
+        double ms = 0.0;
+        apd_eval_get_timing(ctx, nullptr, nullptr, &ms);
+        voxel_ms += ms;
+        return true;
+    };
+    // the reconstruction cut to the volume under T and thinned in the scan's frame: `orig` in its own
+    // coordinates (what the registration takes), `moved` under T
+    int64_t rec_cropped = 0;
+    auto source = [&](const double *T, float voxel, std::vector<float> &orig, std::vector<float> &moved) {
+        std::vector<float> cut, cut_moved;
+        std::vector<int32_t> keep;
+        int64_t nk = 0;
+        if (!crop(in.rec, T, cut) || !transform(cut, T, cut_moved) || !voxel_keep(cut_moved, voxel, keep, nk))
+            return false;
+        rec_cropped = (int64_t)(cut.size() / 3);
+        orig = gather(cut, keep, nk);
+        moved = gather(cut_moved, keep, nk);
+        return true;
+    };
+    std::vector<float> gt_cut;
+    ok = crop(in.gt, nullptr, gt_cut);
+    std::vector<std::pair<float, std::vector<float>>> targets;  // by voxel
+    auto target = [&](float voxel) -> const std::vector<float> * {
+        for (auto &t : targets)
+            if (t.first == voxel) return &t.second;
+        std::vector<int32_t> keep;
+        int64_t nk = 0;
+        if (!voxel_keep(gt_cut, voxel, keep, nk)) return nullptr;
+        targets.emplace_back(voxel, gather(gt_cut, keep, nk));
+        return &targets.back().second;
+    };
+
+    double T[16];
+    mul16(in.init, in.trans, T);
+    std::vector<TatStage> stages;
+    if (!opt.no_refine)
+        for (size_t k = 0; ok && k < opt.stages.size(); ++k) {
+            TatStage s;
+            s.voxel = opt.stages[k].first;
+            s.max_corr = opt.stages[k].second;
+            std::vector<float> src, moved;
+            const std::vector<float> *tgt = nullptr;
+            if (!(ok = source(T, s.voxel, src, moved) && (tgt = target(s.voxel)) != nullptr)) break;
+            s.source_points = (int64_t)(src.size() / 3);
+            s.target_points = (int64_t)(tgt->size() / 3);
+            int st = apd_eval_set_target(ctx, s.target_points, tgt->data());
+            if (st != APD_OK) { ok = fail_ctx(ctx, "apd_eval_set_target", st); break; }
+            double Tn[16];
+            st = apd_eval_register(ctx, s.source_points, src.data(), T, s.max_corr, opt.no_scale ? 0 : 1, 20, 1e-6, 1e-6,
+                                   Tn, &s.info);
+            if (st != APD_OK && st != APD_ESTATE) { ok = fail_ctx(ctx, "apd_eval_register", st); break; }
+            s.ok = st == APD_OK;
+            apd_eval_get_register_timing(ctx, &s.eval_ms, &s.fold_ms, &s.solve_ms, &s.evaluations, nullptr, nullptr);
+            std::copy(Tn, Tn + 16, T);  // on APD_ESTATE: the last transform with 3 correspondences, T itself if none
+            std::printf("stage %zu: voxel %s max_corr %s source %lld target %lld iterations %d n_corr %lld fitness %.6f "
+                        "rmse %.6g%s\n",
+                        k + 1, fmt_f32(s.voxel).c_str(), fmt_f32(s.max_corr).c_str(), (long long)s.source_points,
+                        (long long)s.target_points, s.info.iterations, (long long)s.info.n_corr, s.info.fitness,
+                        s.info.rmse, s.ok ? "" : " (too few correspondences: transform kept)");
+            stages.push_back(s);
+        }
+
+    const float half = opt.tau / 2.0f, strict = std::nextafterf(opt.tau, 0.0f);
+    std::vector<float> src, moved;
+    const std::vector<float> *tgt = nullptr;
+    int64_t within_p = 0, within_r = 0;
+    double build_ms = 0.0, query_ms = 0.0;
+    ok = ok && source(T, half, src, moved) && (tgt = target(half)) != nullptr;
+    if (ok) {
+        auto side = [&](const std::vector<float> &q, const std::vector<float> &t, int64_t &within) {
+            int st = apd_eval_set_target(ctx, (int64_t)(t.size() / 3), t.data());
+            if (st != APD_OK) return fail_ctx(ctx, "apd_eval_set_target", st);
+            st = apd_eval_distances(ctx, (int64_t)(q.size() / 3), q.data(), opt.tau, nullptr, 1, &strict, &within);
+            if (st != APD_OK) return fail_ctx(ctx, "apd_eval_distances", st);
+            double b = 0.0, qm = 0.0;
+            apd_eval_get_timing(ctx, &b, &qm, nullptr);
+            build_ms += b;
+            query_ms += qm;
+            return true;
+        };
+        ok = side(moved, *tgt, within_p) && side(*tgt, moved, within_r);
+    }
+    if (ok && !opt.aligned_out.empty()) {
+        std::vector<float> all;
+        if ((ok = transform(in.rec, T, all))) {
+            const std::vector<uint8_t> rgb(all.size(), 200);
+            if (!write_ply_xyz_rgb(opt.aligned_out, all, rgb)) {
+                std::fprintf(stderr, "apd_eval: cannot write %s\n", opt.aligned_out.c_str());
+                ok = false;
+            }
+        }
+    }
+    apd_eval_destroy(ctx);
+    if (!ok) return 1;
+
+    const int64_t ns = (int64_t)(moved.size() / 3), ng = (int64_t)(tgt->size() / 3);
+    const double P = ns ? (double)within_p / (double)ns : 0.0, R = ng ? (double)within_r / (double)ng : 0.0;
+    const double F = P + R > 0.0 ? 2.0 * P * R / (P + R) : 0.0;
+    std::printf("Tanks and Temples protocol: tau %s, %s, %zu refinement stages\n", fmt_f32(opt.tau).c_str(),
+                opt.no_scale ? "rigid" : "with scale", stages.size());
+    std::printf("source points: %zu in, %lld in the crop volume, %lld after downsampling\n", in.rec.size() / 3,
+                (long long)rec_cropped, (long long)ns);
+    std::printf("target points: %zu in, %zu in the crop volume, %lld after downsampling\n", in.gt.size() / 3,
+                gt_cut.size() / 3, (long long)ng);
+    std::printf("precision: %.6f\nrecall: %.6f\nf-score: %.6f\n", P, R, F);
+    json += std::string("\"tat\": {\"definition\": \"modelled on the Tanks and Temples protocol (crop volume, ICP "
+                        "refinement, voxel downsampling, precision / recall / F-score at tau) with this project's own "
+                        "contract: lowest-index voxel representative, third stage by voxel, no trajectory alignment; "
+                        "parity with the toolbox is not pinned\", \"tau\": ") +
+            fmt_g((double)opt.tau) + ", \"with_scale\": " + (opt.no_scale ? "false" : "true") + ", \"refine\": " +
+            (opt.no_refine ? "false" : "true") + ", \"stages\": [" +
+            join(stages,
+                 [](const TatStage &s) {
+                     return "{\"voxel\": " + fmt_g((double)s.voxel) + ", \"max_corr\": " + fmt_g((double)s.max_corr) +
+                            ", \"source_points\": " + std::to_string(s.source_points) + ", \"target_points\": " +
+                            std::to_string(s.target_points) + ", \"ok\": " + (s.ok ? "true" : "false") +
+                            ", \"iterations\": " + std::to_string(s.info.iterations) + ", \"n_corr\": " +
+                            std::to_string(s.info.n_corr) + ", \"n_finite\": " + std::to_string(s.info.n_finite) +
+                            ", \"fitness\": " + fmt_g(s.info.fitness) + ", \"rmse\": " + fmt_g(s.info.rmse) +
+                            ", \"evaluations\": " + std::to_string(s.evaluations) + ", \"eval_ms\": " + fmt_g(s.eval_ms) +
+                            ", \"fold_ms\": " + fmt_g(s.fold_ms) + ", \"solve_ms\": " + fmt_g(s.solve_ms) + "}";
+                 }) +
+            "], \"transform\": " + json_mat(T) + ", \"source\": {\"points_in\": " + std::to_string(in.rec.size() / 3) +
+            ", \"points_cropped\": " + std::to_string(rec_cropped) + ", \"points\": " + std::to_string(ns) +
+            "}, \"target\": {\"points_in\": " + std::to_string(in.gt.size() / 3) + ", \"points_cropped\": " +
+            std::to_string(gt_cut.size() / 3) + ", \"points\": " + std::to_string(ng) + "}, \"within_precision\": " +
+            std::to_string(within_p) + ", \"within_recall\": " + std::to_string(within_r) + ", \"precision\": " +
+            fmt_g(P) + ", \"recall\": " + fmt_g(R) + ", \"fscore\": " + fmt_g(F) + ", \"crop_ms\": " + fmt_g(crop_ms) +
+            ", \"voxel_ms\": " + fmt_g(voxel_ms) + ", \"transform_ms\": " + fmt_g(transform_ms) + ", \"build_ms\": " +
+            fmt_g(build_ms) + ", \"query_ms\": " + fmt_g(query_ms) + "}";
+    return 0;
+}
+
+// what the readers understood, for tests and for checking a scene's files by eye
+int run_tat_dump(const TatInputs &in, bool have_crop) {
+    double T[16];
+    mul16(in.init, in.trans, T);
+    std::string o = "{\"trans\": " + json_mat(in.trans) + ", \"init\": " + json_mat(in.init) + ", \"transform\": " +
+                    json_mat(T);
+    if (have_crop) {
+        o += std::string(", \"crop\": {\"orthogonal_axis\": \"") + "XYZ"[in.crop.axis] + "\", \"axis_min\": " +
+             fmt_g(in.crop.axis_min) + ", \"axis_max\": " + fmt_g(in.crop.axis_max) + ", \"bounding_polygon\": [";
+        for (size_t i = 0; i + 2 < in.crop.vertices.size(); i += 3)
+            o += std::string(i ? ", " : "") + "[" + fmt_g(in.crop.vertices[i]) + ", " + fmt_g(in.crop.vertices[i + 1]) +
+                 ", " + fmt_g(in.crop.vertices[i + 2]) + "]";
+        o += "]}";
+    }
+    std::printf("%s}\n", o.c_str());
+    return 0;
+}
+
 // ---- depth mode ---------------------------------------------------------------------------------
 
 struct DepthStats {
@@ -852,6 +1115,9 @@ int main(int argc, char **argv) {
             std::fputs(kHelp, stdout);
             return 0;
         }
+        if (a == "--no_refine") { opt.no_refine = true; continue; }
+        if (a == "--no_scale") { opt.no_scale = true; continue; }
+        if (a == "--tat_dump") { opt.tat_dump = true; continue; }
         if (i + 1 >= argc) return bad("missing value for " + a);
         const std::string v = argv[++i];
         if (a == "--cloud") opt.cloud = v;
@@ -868,6 +1134,28 @@ int main(int argc, char **argv) {
         else if (a == "--gt_mlp") opt.gt_mlp = v;
         else if (a == "--accuracy_cloud_out") opt.accuracy_out = v;
         else if (a == "--completeness_cloud_out") opt.completeness_out = v;
+        else if (a == "--tat_gt") opt.tat_gt = v;
+        else if (a == "--tat_crop") opt.tat_crop = v;
+        else if (a == "--tat_trans") opt.tat_trans = v;
+        else if (a == "--init_trans") opt.init_trans = v;
+        else if (a == "--aligned_cloud_out") opt.aligned_out = v;
+        else if (a == "--tau") {
+            if (!parse_float(v, opt.tau) || !(opt.tau > 0.0f) || !std::isfinite(opt.tau)) return bad("bad --tau " + v);
+            opt.tau_given = true;
+        } else if (a == "--refine_stages") {
+            std::istringstream ss(v);
+            std::string tok;
+            while (std::getline(ss, tok, ',')) {
+                const size_t c = tok.find(':');
+                float vox, mc;
+                if (c == std::string::npos || !parse_float(tok.substr(0, c), vox) || !parse_float(tok.substr(c + 1), mc) ||
+                    !(vox > 0.0f) || !std::isfinite(vox) || !(mc > 0.0f) || !std::isfinite(mc))
+                    return bad("bad refinement stage '" + tok + "' (voxel:max_corr, both positive)");
+                opt.stages.emplace_back(vox, mc);
+            }
+            if (opt.stages.empty() || opt.stages.size() > 16) return bad("--refine_stages takes 1 to 16 stages");
+            opt.stages_given = true;
+        }
         else if (a == "--cube_size") {
             if (!parse_int(v, opt.cube_size) || opt.cube_size < 2 || opt.cube_size > 16384)
                 return bad("bad --cube_size " + v + " (2..16384)");
@@ -902,8 +1190,9 @@ int main(int argc, char **argv) {
             return bad("unknown option " + a);
         }
     }
+    const bool tat_mode = !opt.tat_gt.empty() || opt.tat_dump;
     const bool scanner_mode = !opt.gt_mlp.empty();
-    const bool cloud_mode = !scanner_mode && (!opt.cloud.empty() || !opt.gt.empty());
+    const bool cloud_mode = !scanner_mode && !tat_mode && (!opt.cloud.empty() || !opt.gt.empty());
     const bool depth_mode = !opt.dense.empty() || !opt.against.empty() || !opt.gt_depth.empty() || !opt.gt_cloud.empty();
     const bool render_mode = !opt.render_gt.empty();
     if (scanner_mode) {
@@ -920,7 +1209,23 @@ int main(int argc, char **argv) {
     } else if (opt.cube_given || !opt.accuracy_out.empty() || !opt.completeness_out.empty()) {
         return bad("--cube_size / --accuracy_cloud_out / --completeness_cloud_out without --gt_mlp");
     }
-    if (!cloud_mode && !depth_mode && !render_mode && !scanner_mode) return bad("nothing to do");
+    if (tat_mode) {
+        if (scanner_mode || depth_mode || render_mode || !opt.gt.empty() || opt.visible_views > 0 || !opt.scan.empty() ||
+            opt.voxel_given)
+            return bad("--tat_gt excludes the other modes and their options");
+        if (opt.no_refine && opt.stages_given) return bad("--no_refine with --refine_stages");
+        if (!opt.tat_dump) {
+            if (opt.cloud.empty() || opt.tat_gt.empty() || opt.tat_crop.empty() || !opt.tau_given)
+                return bad("Tanks and Temples mode needs --cloud, --tat_gt, --tat_crop and --tau");
+            if (!opt.stages_given)
+                opt.stages = {{opt.tau, 80.0f * opt.tau}, {opt.tau / 2.0f, 20.0f * opt.tau}, {opt.tau / 2.0f, 2.0f * opt.tau}};
+        }
+    } else if (!opt.tat_crop.empty() || !opt.tat_trans.empty() || !opt.init_trans.empty() || !opt.aligned_out.empty() ||
+               opt.tau_given || opt.no_refine || opt.no_scale || opt.stages_given) {
+        return bad("--tat_crop / --tat_trans / --init_trans / --tau / --no_refine / --refine_stages / --no_scale / "
+                   "--aligned_cloud_out without --tat_gt");
+    }
+    if (!cloud_mode && !depth_mode && !render_mode && !scanner_mode && !tat_mode) return bad("nothing to do");
     if (cloud_mode && (opt.cloud.empty() || opt.gt.empty())) return bad("cloud mode needs --cloud and --gt");
     if (depth_mode && (opt.dense.empty() ||
                        (int)!opt.against.empty() + (int)!opt.gt_depth.empty() + (int)!opt.gt_cloud.empty() != 1))
@@ -943,6 +1248,7 @@ int main(int argc, char **argv) {
     CloudInputs cin;
     RenderInputs rin;
     ScannerInputs sin;
+    TatInputs tin;
     std::string err;
     auto unreadable = [&] {
         std::fprintf(stderr, "apd_eval: %s\n", err.c_str());
@@ -960,6 +1266,16 @@ int main(int argc, char **argv) {
     }
     if (render_mode && (!read_ply_xyz(opt.render_gt, rin.xyz, err) || !load_scan_views(opt.scan, rin.views, err)))
         return unreadable();
+    if (tat_mode) {
+        identity16(tin.trans);
+        identity16(tin.init);
+        if ((!opt.tat_crop.empty() && !read_tat_crop(opt.tat_crop, tin.crop, err)) ||
+            (!opt.tat_trans.empty() && !read_matrix4(opt.tat_trans, tin.trans, err)) ||
+            (!opt.init_trans.empty() && !read_matrix4(opt.init_trans, tin.init, err)))
+            return unreadable();
+        if (opt.tat_dump) return run_tat_dump(tin, !opt.tat_crop.empty());
+        if (!read_ply_xyz(opt.cloud, tin.rec, err) || !read_ply_xyz(opt.tat_gt, tin.gt, err)) return unreadable();
+    }
     if (scanner_mode) {
         std::vector<MlpMesh> meshes;
         if (!read_ply_xyz(opt.cloud, sin.rec.xyz, err) || !read_mlp(opt.gt_mlp, meshes, err)) return unreadable();
@@ -999,6 +1315,12 @@ int main(int argc, char **argv) {
         const int st = run_scanners(opt, sin, json);
         status = std::max(status, st);
         if (st != 0) json += "\"scanners\": null";
+    }
+    if (tat_mode) {
+        sep();
+        const int st = run_tat(opt, tin, json);
+        status = std::max(status, st);
+        if (st != 0) json += "\"tat\": null";
     }
     if (render_mode) {
         sep();

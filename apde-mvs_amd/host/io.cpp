@@ -419,6 +419,263 @@ void mlp_to_world(const MlpMesh &m, std::vector<float> &xyz, float origin[3]) {
     for (int r = 0; r < 3; ++r) origin[r] = (float)M[4 * r + 3];
 }
 
+// ----------------------------------------------------------------------------------------------
+// Tanks and Temples side files
+// ----------------------------------------------------------------------------------------------
+namespace {
+
+bool read_text_bounded(const std::string &path, size_t cap, const char *cap_name, std::string &text, std::string &err) {
+    std::ifstream in(path, std::ios::binary);
+    if (!in) { err = "cannot open " + path; return false; }
+    text.clear();
+    for (char buf[1 << 16]; in.read(buf, sizeof buf) || in.gcount() > 0;) {  // a directory opens but does not read
+        text.append(buf, (size_t)in.gcount());
+        if (text.size() > cap) { err = path + ": larger than " + cap_name; return false; }
+    }
+    if (in.bad()) { err = path + ": read error"; return false; }
+    return true;
+}
+
+// Recursive-descent JSON over a string; values outside the wanted keys are validated and dropped.
+struct JsonCursor {
+    const std::string &s;
+    size_t p = 0;
+    std::string err;
+    explicit JsonCursor(const std::string &text) : s(text) {}
+    static constexpr int kMaxDepth = 64;
+
+    bool fail(const std::string &what) {
+        if (err.empty()) err = what + " at byte " + std::to_string(p);
+        return false;
+    }
+    void ws() {
+        while (p < s.size() && (s[p] == ' ' || s[p] == '\t' || s[p] == '\n' || s[p] == '\r')) ++p;
+    }
+    bool lit(const char *word) {
+        const size_t n = std::strlen(word);
+        if (s.compare(p, n, word) != 0) return fail("unexpected token");
+        p += n;
+        return true;
+    }
+    bool string(std::string &out) {
+        if (p >= s.size() || s[p] != '"') return fail("expected a string");
+        ++p;
+        out.clear();
+        while (p < s.size()) {
+            const unsigned char c = (unsigned char)s[p];
+            if (c == '"') { ++p; return true; }
+            if (c < 0x20) return fail("control character in a string");
+            if (c == '\\') {
+                if (p + 1 >= s.size()) break;
+                const char e = s[p + 1];
+                if (e == 'u') {
+                    if (p + 6 > s.size()) break;
+                    for (size_t k = p + 2; k < p + 6; ++k)
+                        if (!std::isxdigit((unsigned char)s[k])) return fail("bad \\u escape");
+                    out.push_back('?');  // no wanted string holds an escape: the code point is not needed
+                    p += 6;
+                    continue;
+                }
+                if (!std::strchr("\"\\/bfnrt", e) || e == '\0') return fail("bad escape");
+                out.push_back(e);
+                p += 2;
+                continue;
+            }
+            if (out.size() < 4096) out.push_back((char)c);
+            ++p;
+        }
+        return fail("unterminated string");
+    }
+    bool number(double &v) {
+        const size_t b = p;
+        if (p < s.size() && s[p] == '-') ++p;
+        if (p >= s.size() || !std::isdigit((unsigned char)s[p])) return fail("expected a number");
+        if (s[p] == '0') ++p;
+        else while (p < s.size() && std::isdigit((unsigned char)s[p])) ++p;
+        if (p < s.size() && s[p] == '.') {
+            ++p;
+            if (p >= s.size() || !std::isdigit((unsigned char)s[p])) return fail("digits expected after '.'");
+            while (p < s.size() && std::isdigit((unsigned char)s[p])) ++p;
+        }
+        if (p < s.size() && (s[p] == 'e' || s[p] == 'E')) {
+            ++p;
+            if (p < s.size() && (s[p] == '+' || s[p] == '-')) ++p;
+            if (p >= s.size() || !std::isdigit((unsigned char)s[p])) return fail("digits expected in the exponent");
+            while (p < s.size() && std::isdigit((unsigned char)s[p])) ++p;
+        }
+        if (p - b > 400) return fail("number token longer than 400 characters");
+        // std::from_chars: no locale, and a token of this grammar is all it accepts here
+        const std::from_chars_result r = std::from_chars(s.data() + b, s.data() + p, v);
+        if (r.ec != std::errc() || r.ptr != s.data() + p || !std::isfinite(v)) {
+            p = b;
+            return fail("number outside the double range");
+        }
+        return true;
+    }
+    // any value, validated and dropped
+    bool skip(int depth) {
+        if (depth > kMaxDepth) return fail("nesting deeper than 64");
+        ws();
+        if (p >= s.size()) return fail("unexpected end of file");
+        const char c = s[p];
+        std::string str;
+        double v;
+        if (c == '"') return string(str);
+        if (c == 't') return lit("true");
+        if (c == 'f') return lit("false");
+        if (c == 'n') return lit("null");
+        if (c == '[') {
+            ++p;
+            ws();
+            if (p < s.size() && s[p] == ']') { ++p; return true; }
+            for (;;) {
+                if (!skip(depth + 1)) return false;
+                ws();
+                if (p < s.size() && s[p] == ',') { ++p; continue; }
+                if (p < s.size() && s[p] == ']') { ++p; return true; }
+                return fail("expected ',' or ']'");
+            }
+        }
+        if (c == '{') {
+            ++p;
+            ws();
+            if (p < s.size() && s[p] == '}') { ++p; return true; }
+            for (;;) {
+                ws();
+                if (!string(str)) return false;
+                ws();
+                if (p >= s.size() || s[p] != ':') return fail("expected ':'");
+                ++p;
+                if (!skip(depth + 1)) return false;
+                ws();
+                if (p < s.size() && s[p] == ',') { ++p; continue; }
+                if (p < s.size() && s[p] == '}') { ++p; return true; }
+                return fail("expected ',' or '}'");
+            }
+        }
+        return number(v);
+    }
+};
+
+}  // namespace
+
+std::vector<double> TatCrop::polygon() const {
+    const int ui = axis == 0 ? 1 : 0, vi = axis == 2 ? 1 : 2;
+    std::vector<double> uv;
+    for (size_t i = 0; i + 2 < vertices.size(); i += 3) {
+        uv.push_back(vertices[i + (size_t)ui]);
+        uv.push_back(vertices[i + (size_t)vi]);
+    }
+    return uv;
+}
+
+bool read_tat_crop(const std::string &path, TatCrop &crop, std::string &err) {
+    crop = TatCrop{};
+    std::string text;
+    if (!read_text_bounded(path, (size_t)64 << 20, "64 MiB", text, err)) return false;
+    JsonCursor js(text);
+    auto fail = [&](const std::string &what) {
+        err = path + ": " + (js.err.empty() ? what : js.err);
+        crop = TatCrop{};
+        return false;
+    };
+    js.ws();
+    if (js.p >= text.size() || text[js.p] != '{') return fail("not a JSON object");
+    ++js.p;
+    bool have_min = false, have_max = false, have_axis = false, have_poly = false;
+    js.ws();
+    if (js.p < text.size() && text[js.p] == '}') {
+        ++js.p;
+    } else {
+        for (;;) {
+            std::string key, sval;
+            js.ws();
+            if (!js.string(key)) return fail("");
+            js.ws();
+            if (js.p >= text.size() || text[js.p] != ':') return fail("expected ':' after a key");
+            ++js.p;
+            js.ws();
+            if (key == "axis_min" || key == "axis_max") {
+                bool &have = key == "axis_min" ? have_min : have_max;
+                if (have) return fail("key " + key + " is repeated");
+                if (!js.number(key == "axis_min" ? crop.axis_min : crop.axis_max)) return fail("");
+                have = true;
+            } else if (key == "orthogonal_axis") {
+                if (have_axis) return fail("key orthogonal_axis is repeated");
+                if (!js.string(sval)) return fail("");
+                if (sval != "X" && sval != "Y" && sval != "Z") return fail("orthogonal_axis is not \"X\", \"Y\" or \"Z\"");
+                crop.axis = sval[0] - 'X';
+                have_axis = true;
+            } else if (key == "bounding_polygon") {
+                if (have_poly) return fail("key bounding_polygon is repeated");
+                if (js.p >= text.size() || text[js.p] != '[') return fail("bounding_polygon is not an array");
+                ++js.p;
+                js.ws();
+                if (js.p < text.size() && text[js.p] == ']') {
+                    ++js.p;
+                } else {
+                    for (;;) {
+                        js.ws();
+                        if (js.p >= text.size() || text[js.p] != '[') return fail("a polygon vertex is not an array");
+                        ++js.p;
+                        if (crop.vertices.size() / 3 >= ((size_t)1 << 20)) return fail("more than 2^20 polygon vertices");
+                        for (int k = 0; k < 3; ++k) {
+                            double v;
+                            js.ws();
+                            if (!js.number(v)) return fail("");
+                            crop.vertices.push_back(v);
+                            js.ws();
+                            if (js.p >= text.size() || text[js.p] != (k < 2 ? ',' : ']'))
+                                return fail("a polygon vertex does not have exactly three numbers");
+                            ++js.p;
+                        }
+                        js.ws();
+                        if (js.p < text.size() && text[js.p] == ',') { ++js.p; continue; }
+                        if (js.p < text.size() && text[js.p] == ']') { ++js.p; break; }
+                        return fail("expected ',' or ']' in bounding_polygon");
+                    }
+                }
+                have_poly = true;
+            } else if (!js.skip(1)) {
+                return fail("");
+            }
+            js.ws();
+            if (js.p < text.size() && text[js.p] == ',') { ++js.p; continue; }
+            if (js.p < text.size() && text[js.p] == '}') { ++js.p; break; }
+            return fail("expected ',' or '}'");
+        }
+    }
+    js.ws();
+    if (js.p != text.size()) return fail("data after the closing brace");
+    if (!have_min || !have_max || !have_axis || !have_poly)
+        return fail("axis_min, axis_max, orthogonal_axis or bounding_polygon is missing");
+    if (crop.vertices.size() / 3 < 3) return fail("bounding_polygon has fewer than 3 vertices");
+    return true;
+}
+
+bool read_matrix4(const std::string &path, double M[16], std::string &err) {
+    std::string text;
+    if (!read_text_bounded(path, (size_t)1 << 20, "1 MiB", text, err)) return false;
+    auto fail = [&](const std::string &what) { err = path + ": " + what; return false; };
+    int k = 0;
+    for (size_t p = 0; p < text.size();) {
+        if (std::isspace((unsigned char)text[p])) { ++p; continue; }
+        size_t e = p;
+        while (e < text.size() && !std::isspace((unsigned char)text[e])) ++e;
+        if (e - p > 400) return fail("a token longer than 400 characters");
+        const std::string tok = text.substr(p, e - p);
+        JsonCursor num(tok);  // the JSON number grammar: no hex floats, no inf / nan, no locale
+        double v;
+        if (!num.number(v) || num.p != tok.size()) return fail("'" + tok.substr(0, 32) + "' is not a finite number");
+        if (k >= 16) return fail("more than 16 numbers, a 4x4 matrix expected");
+        M[k++] = v;
+        p = e;
+    }
+    if (k < 16) return fail(std::to_string(k) + " numbers, 16 (a 4x4 matrix) expected");
+    if (M[12] != 0.0 || M[13] != 0.0 || M[14] != 0.0 || M[15] != 1.0) return fail("the last row is not 0 0 0 1");
+    return true;
+}
+
 std::string format_index(int id) {
     std::ostringstream ss;
     ss << std::setw(8) << std::setfill('0') << id;

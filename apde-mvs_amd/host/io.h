@@ -124,6 +124,27 @@ bool read_mlp(const std::string &path, std::vector<MlpMesh> &meshes, std::string
 // right and rounded once to float. origin = the translation column rounded to float: the scanner.
 void mlp_to_world(const MlpMesh &m, std::vector<float> &xyz, float origin[3]);
 
+// ---- Tanks and Temples ground-truth side files (apd_eval --tat_gt) ------------------------------------
+// The crop volume <Scene>.json (Open3D's SelectionPolygonVolume): a JSON object of which only the keys
+// axis_max, axis_min (numbers), orthogonal_axis ("X", "Y" or "Z") and bounding_polygon (an array of
+// 3 to 2^20 arrays of exactly three numbers) are taken; every other key is parsed and ignored.
+struct TatCrop {
+    int axis = 0;  // 0, 1, 2 for X, Y, Z
+    double axis_min = 0.0, axis_max = 0.0;
+    std::vector<double> vertices;  // 3 per vertex, as in the file
+    // the (u, v) pairs of include/apd_eval.h's crop rule: coordinates (1, 2), (0, 2), (0, 1) for X, Y, Z
+    std::vector<double> polygon() const;
+};
+// A minimal strict JSON parser (RFC 8259 syntax, no extensions): files over 64 MiB, nesting deeper than
+// 64, a missing or repeated wanted key, a wrong type, a number outside the double range, a vertex count
+// outside 3..2^20 and anything after the closing brace are rejected with a message in `err`.
+bool read_tat_crop(const std::string &path, TatCrop &crop, std::string &err);
+// A 4x4 matrix as 16 numbers separated by white space (<Scene>_trans.txt), row-major. A number has the
+// JSON grammar (-?digits[.digits][e[+-]digits], as in the crop file; read without regard to the locale).
+// Rejected: files over 1 MiB, fewer or more than 16 tokens, a token that is no such number (hex floats,
+// inf, nan, a leading '+' or '.') or lies outside the double range, a last row other than 0 0 0 1.
+bool read_matrix4(const std::string &path, double M[16], std::string &err);
+
 // ---- COLMAP sparse models (apd_prepare; the reference's tools/colmap2mvsnet.py) ---------------------
 struct ColmapCamera {
     uint32_t id = 0;

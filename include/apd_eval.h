@@ -8,7 +8,9 @@
  * tool's free-space and visibility handling is not modelled. A z-buffer renderer of a cloud into
  * cameras and a per-point visibility count against depth maps serve a plain visibility filter.
  * A scanner free-space test and voxel-averaged scores, modelled on the ETH3D protocol with a contract
- * of their own, are declared at the end of this header (parity with the ETH3D tool is not pinned).
+ * of their own, are declared after them (parity with the ETH3D tool is not pinned). A crop volume,
+ * the nearest neighbour with its index, a similarity transform and point-to-point ICP registration, the
+ * steps of the Tanks and Temples protocol, close the header, each with a host twin.
  *
  * Distance contract (bit for bit, all arithmetic fp32 and nothing contracted):
  *   - a target with a non-finite coordinate never matches; a query with one gives +inf
@@ -174,6 +176,113 @@ int32_t apd_eval_voxel_scores(apd_eval_ctx *ctx, int64_t n, const float *xyz, fl
 /* Device-event times of the last free_gap (kernels only) and voxel_scores (keys, sort, scans and
    sums) call, in ms. Any pointer may be NULL. */
 int32_t apd_eval_get_protocol_timing(apd_eval_ctx *ctx, double *free_gap_ms, double *scores_ms);
+
+/* ---- crop volume, nearest neighbour with index, registration ---------------------------------------
+ * The steps the Tanks and Temples evaluation protocol adds in front of the distances: the
+ * reconstruction is moved into the scan's frame by a similarity that point-to-point ICP refines, and
+ * both clouds are cut to a crop volume. The contract is this project's own (bit for bit between the
+ * device calls and their host twins, and the same from run to run); parity with the Tanks and Temples
+ * toolbox is not pinned. Doubles throughout, nothing contracted.
+ *
+ * Transform. T is a 4x4 double matrix, row-major; NULL means identity. For a point (x, y, z), each
+ * converted to double, row r gives
+ *     p'[r] = ((T[4r]*x + T[4r+1]*y) + T[4r+2]*z) + T[4r+3]         (the last row of T is not read)
+ * and q = the fp32 rounding of p' (apd_eval_transform writes q; a non-finite input gives whatever the
+ * arithmetic gives).
+ *
+ * Crop rule (Open3D's SelectionPolygonVolume). With axis in {0, 1, 2} for X, Y, Z, (u, v, w) are the
+ * coordinates (1, 2, 0), (0, 2, 1), (0, 1, 2) of p' (p' = the point itself, in double, when T is
+ * NULL). The polygon is m >= 3 vertices as (U, V) double pairs. A point is kept iff its three input
+ * coordinates and p' are finite, axis_min <= p'[w] <= axis_max, and the number of edges (i, (i+1) mod m)
+ * with  (Vi > pv) != (Vj > pv)  and  pu < ((Uj - Ui)*(pv - Vi))/(Vj - Vi) + Ui  is odd.
+ *
+ * Nearest neighbour with index: apd_eval_distances' contract, plus idx[i] = the lowest index (in the
+ * array given to apd_eval_set_target) among the targets that attain the minimal d2; -1 where the
+ * result is +inf.
+ *
+ * Registration: point-to-point ICP of a source cloud against the current target. One evaluation of a
+ * transform T yields 19 double sums over the source points i. q_i is the transform above; its
+ * correspondence t_i is the target idx of q_i under max_dist = max_corr; it has none if that idx is
+ * -1 (which includes a non-finite q_i). The terms of a point with a correspondence, coordinates
+ * converted to double:
+ *     [0] 1   [1..3] q   [4..6] t   [7 + 3a + b] q_a*t_b   [16] (qx*qx + qy*qy) + qz*qz
+ *     [17] the fp32 minimal d2 of the distance contract, converted to double
+ * and +0.0 each for a point without one; [18] is 1 for every point with a finite q_i, else +0.0.
+ * Summation order: the source indices are cut into blocks of APD_EVAL_REG_BLOCK = 1024, the last one
+ * padded with +0.0 terms; within a block the terms are summed by the balanced binary tree over the
+ * index ((0+1)+(2+3))+...; the block sums are added left to right in block order, starting from block
+ * 0's sum (no block: +0.0).
+ *     n_corr = [0], n_finite = [18], fitness = n_corr / n_finite (0 if n_finite is 0),
+ *     rmse = sqrt([17] / n_corr) (0 if n_corr is 0).
+ * Solve (Umeyama, on the host in double): N = [0], mu_q = [1..3]/N, mu_t = [4..6]/N,
+ *     C[a][b] = [7 + 3b + a]/N - mu_t[a]*mu_q[b],  var_q = [16]/N - |mu_q|^2,
+ *     C = U D V^T by one-sided Jacobi rotations (the project's own 3x3 SVD, D descending),
+ *     g = sign(det(U V^T)),  R = U diag(1, 1, g) V^T,  s = (D0 + D1 + g*D2)/var_q with with_scale, else 1,
+ *     t = mu_t - s R mu_q,  T <- [sR | t] T.
+ * Loop: evaluate T (initially T0); stop if fewer than 3 correspondences (APD_ESTATE); stop if this is
+ * not the first evaluation and both |fitness - previous| < eps_fitness and |rmse - previous| <
+ * eps_rmse (Open3D's rule); stop after max_iter updates; else solve, update, repeat. T is therefore
+ * evaluated once more after its last update and info describes the returned T. On APD_ESTATE (fewer
+ * than 3 correspondences, a covariance of rank < 2, no spread in q with with_scale) T is the last
+ * transform whose evaluation had at least 3 correspondences (T0 if none) and info holds the last
+ * evaluation's numbers.
+ */
+#define APD_EVAL_REG_BLOCK 1024
+
+typedef struct apd_eval_reg_info {
+    int32_t iterations; /* updates applied to T0 */
+    int32_t reserved;
+    int64_t n_corr;
+    int64_t n_finite;
+    double fitness;
+    double rmse;
+} apd_eval_reg_info;
+
+/* keep_idx (room for n entries): the ascending indices of the kept points, *n_keep their number.
+   poly: m (U, V) pairs, host memory, as are T and the scalars. xyz, keep_idx, n_keep: host or device.
+   APD_EINVAL: n out of range, a NULL pointer with n > 0, n_keep or poly NULL, m < 3 or m > 2^20, a
+   non-finite polygon entry, bound or entry of T, axis outside 0..2. */
+int32_t apd_eval_crop_volume(apd_eval_ctx *ctx, int64_t n, const float *xyz, const double *T, int32_t axis,
+                             double axis_min, double axis_max, int32_t m, const double *poly, int32_t *keep_idx,
+                             int64_t *n_keep);
+/* Host twin: one thread, no context, no device; every pointer is host memory. */
+int32_t apd_eval_crop_volume_host(int64_t n, const float *xyz, const double *T, int32_t axis, double axis_min,
+                                  double axis_max, int32_t m, const double *poly, int32_t *keep_idx, int64_t *n_keep);
+
+/* dist (n floats) and idx (n int32) may each be NULL; host or device pointers.
+   APD_EINVAL / APD_ESTATE as apd_eval_distances. */
+int32_t apd_eval_nearest(apd_eval_ctx *ctx, int64_t n, const float *xyz, float max_dist, float *dist, int32_t *idx);
+/* Host twin against nt target points (a uniform grid when max_dist allows one, else brute force). */
+int32_t apd_eval_nearest_host(int64_t nt, const float *target, int64_t n, const float *xyz, float max_dist,
+                              float *dist, int32_t *idx);
+
+/* out (n*3 floats) = q of every point; xyz and out may be host or device pointers and may coincide.
+   APD_EINVAL: n out of range, a NULL pointer with n > 0, a non-finite entry of T. */
+int32_t apd_eval_transform(apd_eval_ctx *ctx, int64_t n, const float *xyz, const double *T, float *out);
+int32_t apd_eval_transform_host(int64_t n, const float *xyz, const double *T, float *out);
+
+/* T0 (may be NULL), T (16 doubles) and info are host memory; xyz is a host or a device pointer.
+   APD_EINVAL: n out of range, xyz NULL with n > 0, T or info NULL, a non-finite entry of T0, max_corr
+   not positive and finite, with_scale outside 0..1, max_iter outside 1..1000, an eps negative or NaN.
+   APD_ESTATE: no apd_eval_set_target before, or as described above. */
+int32_t apd_eval_register(apd_eval_ctx *ctx, int64_t n, const float *xyz, const double *T0, float max_corr,
+                          int32_t with_scale, int32_t max_iter, double eps_fitness, double eps_rmse, double *T,
+                          apd_eval_reg_info *info);
+int32_t apd_eval_register_host(int64_t nt, const float *target, int64_t n, const float *xyz, const double *T0,
+                               float max_corr, int32_t with_scale, int32_t max_iter, double eps_fitness,
+                               double eps_rmse, double *T, apd_eval_reg_info *info);
+/* The 19 sums of one evaluation of T (NULL: identity), for tests and tools. sums: host memory. */
+int32_t apd_eval_register_sums(apd_eval_ctx *ctx, int64_t n, const float *xyz, const double *T, float max_corr,
+                               double *sums);
+int32_t apd_eval_register_sums_host(int64_t nt, const float *target, int64_t n, const float *xyz, const double *T,
+                                    float max_corr, double *sums);
+
+/* Of the last apd_eval_register / apd_eval_register_sums call: the device-event time of the fused
+   evaluation kernels and of the folds (sums over the evaluations), the host time of the solves, and
+   the number of evaluations. crop_ms / transform_ms: the last crop_volume / transform call's kernels.
+   Any pointer may be NULL. */
+int32_t apd_eval_get_register_timing(apd_eval_ctx *ctx, double *eval_ms, double *fold_ms, double *solve_ms,
+                                     int32_t *evaluations, double *crop_ms, double *transform_ms);
 
 #ifdef __cplusplus
 }
