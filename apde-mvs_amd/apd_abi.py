@@ -237,7 +237,10 @@ EVAL_EXPORTS = ["apd_eval_create", "apd_eval_destroy", "apd_eval_last_error", "a
                 "apd_eval_get_protocol_timing",
                 "apd_eval_crop_volume", "apd_eval_crop_volume_host", "apd_eval_nearest", "apd_eval_nearest_host",
                 "apd_eval_transform", "apd_eval_transform_host", "apd_eval_register", "apd_eval_register_host",
-                "apd_eval_register_sums", "apd_eval_register_sums_host", "apd_eval_get_register_timing"]
+                "apd_eval_register_sums", "apd_eval_register_sums_host", "apd_eval_get_register_timing",
+                "apd_eval_radius_thin", "apd_eval_radius_thin_host", "apd_eval_get_thin_timing", "apd_eval_dtu_ranks",
+                "apd_eval_obs_mask", "apd_eval_obs_mask_host", "apd_eval_half_space", "apd_eval_half_space_host",
+                "apd_eval_masked_stats", "apd_eval_masked_stats_host", "apd_eval_get_dtu_timing"]
 REG_BLOCK = 1024  # APD_EVAL_REG_BLOCK
 REG_SUMS = 19
 
@@ -430,6 +433,34 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     lib.apd_eval_get_register_timing.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double),
                                                  C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_double),
                                                  C.POINTER(C.c_double)]
+    thin_tail = [C.c_int64, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.apd_eval_radius_thin.restype = C.c_int32
+    lib.apd_eval_radius_thin.argtypes = [C.c_void_p] + thin_tail
+    lib.apd_eval_radius_thin_host.restype = C.c_int32
+    lib.apd_eval_radius_thin_host.argtypes = thin_tail
+    lib.apd_eval_get_thin_timing.restype = C.c_int32
+    lib.apd_eval_get_thin_timing.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                             C.POINTER(C.c_int32)]
+    lib.apd_eval_dtu_ranks.restype = C.c_int32
+    lib.apd_eval_dtu_ranks.argtypes = [C.c_int64, C.c_uint32, C.c_void_p]
+    mask_tail = [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p]
+    lib.apd_eval_obs_mask.restype = C.c_int32
+    lib.apd_eval_obs_mask.argtypes = [C.c_void_p] + mask_tail
+    lib.apd_eval_obs_mask_host.restype = C.c_int32
+    lib.apd_eval_obs_mask_host.argtypes = mask_tail
+    lib.apd_eval_half_space.restype = C.c_int32
+    lib.apd_eval_half_space.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.apd_eval_half_space_host.restype = C.c_int32
+    lib.apd_eval_half_space_host.argtypes = [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
+    stats_tail = [C.c_int64, C.c_void_p, C.c_void_p, C.c_float, C.POINTER(C.c_int64), C.POINTER(C.c_double),
+                  C.POINTER(C.c_double)]
+    lib.apd_eval_masked_stats.restype = C.c_int32
+    lib.apd_eval_masked_stats.argtypes = [C.c_void_p] + stats_tail
+    lib.apd_eval_masked_stats_host.restype = C.c_int32
+    lib.apd_eval_masked_stats_host.argtypes = stats_tail
+    lib.apd_eval_get_dtu_timing.restype = C.c_int32
+    lib.apd_eval_get_dtu_timing.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                            C.POINTER(C.c_double)]
     # include/apd_prep.h
     lib.apd_prep_create.restype = C.c_void_p
     lib.apd_prep_create.argtypes = [C.c_int32]
@@ -636,10 +667,95 @@ def register_host(target, xyz, max_corr: float, T0=None, with_scale: bool = True
     return T.reshape(4, 4), info.as_dict(), st
 
 
+def dtu_ranks(n: int, seed: int = 0, lib: Optional[C.CDLL] = None) -> np.ndarray:
+    """rank[i] = word 0 of Philox4x32-10 with counter (i, 0, 0, 0) and key (seed, 0): the order in which
+    `apd_eval --dtu_gt` thins a cloud (apd_eval_dtu_ranks). Needs no GPU."""
+    lib = lib or load_library()
+    rank = np.empty(int(n), np.uint32)
+    _host_status(lib.apd_eval_dtu_ranks(int(n), int(seed) & 0xFFFFFFFF, rank.ctypes.data if n else None),
+                 "apd_eval_dtu_ranks")
+    return rank
+
+
+def _host_rank(rank, n: int):
+    if rank is None:
+        return None
+    r = np.ascontiguousarray(rank, np.uint32).reshape(-1)
+    if len(r) != n:
+        raise ValueError("rank holds one uint32 per point")
+    return r
+
+
+def _mask_geometry(mask, origin):
+    m = np.asarray(mask)
+    if m.ndim != 3:
+        raise ValueError("a mask is a 3-D array")
+    # bytes in MATLAB's column-major order: the first index runs fastest
+    flat = np.ascontiguousarray((m != 0).astype(np.uint8).ravel(order="F"))
+    dims = np.ascontiguousarray(m.shape, np.int32)
+    org = np.ascontiguousarray(origin, np.float64).reshape(-1)
+    if org.size != 3:
+        raise ValueError("origin is three doubles")
+    return flat, dims, org
+
+
+def radius_thin_host(xyz, radius: float, rank=None, lib: Optional[C.CDLL] = None) -> np.ndarray:
+    """apd_eval_radius_thin_host: the ascending indices of the greedy radius thinning. Needs no GPU."""
+    lib = lib or load_library()
+    a, n, addr = _host_cloud(xyz)
+    r = _host_rank(rank, n)
+    keep = np.empty(max(n, 1), np.int32)
+    n_keep = C.c_int64(0)
+    _host_status(lib.apd_eval_radius_thin_host(n, addr, radius, None if r is None or n == 0 else r.ctypes.data,
+                                               keep.ctypes.data, C.addressof(n_keep)), "apd_eval_radius_thin_host")
+    return keep[:n_keep.value].copy()
+
+
+def obs_mask_host(xyz, mask, origin, res: float, lib: Optional[C.CDLL] = None) -> np.ndarray:
+    """apd_eval_obs_mask_host: uint8[n], 1 where the point lies in a set cell of the 3-D mask."""
+    lib = lib or load_library()
+    a, n, addr = _host_cloud(xyz)
+    flat, dims, org = _mask_geometry(mask, origin)
+    inside = np.zeros(n, np.uint8)
+    _host_status(lib.apd_eval_obs_mask_host(n, addr, dims.ctypes.data, org.ctypes.data, float(res), flat.ctypes.data,
+                                            inside.ctypes.data if n else None), "apd_eval_obs_mask_host")
+    return inside
+
+
+def half_space_host(xyz, plane, lib: Optional[C.CDLL] = None) -> np.ndarray:
+    """apd_eval_half_space_host: uint8[n], 1 where P0 x + P1 y + P2 z + P3 > 0."""
+    lib = lib or load_library()
+    a, n, addr = _host_cloud(xyz)
+    P = np.ascontiguousarray(plane, np.float64).reshape(-1)
+    if P.size != 4:
+        raise ValueError("a plane is four doubles")
+    above = np.zeros(n, np.uint8)
+    _host_status(lib.apd_eval_half_space_host(n, addr, P.ctypes.data, above.ctypes.data if n else None),
+                 "apd_eval_half_space_host")
+    return above
+
+
+def masked_stats_host(dist, flag, limit: float, lib: Optional[C.CDLL] = None) -> dict:
+    """apd_eval_masked_stats_host: {"count", "sum", "median"} of the distances with flag set (None: all)
+    that are <= limit."""
+    lib = lib or load_library()
+    d = np.ascontiguousarray(dist, np.float32).reshape(-1)
+    f = None if flag is None else np.ascontiguousarray(flag, np.uint8).reshape(-1)
+    if f is not None and len(f) != len(d):
+        raise ValueError("flag holds one byte per distance")
+    n = len(d)
+    c, s, m = C.c_int64(0), C.c_double(0.0), C.c_double(0.0)
+    _host_status(lib.apd_eval_masked_stats_host(n, d.ctypes.data if n else None,
+                                                None if f is None or n == 0 else f.ctypes.data, limit, C.byref(c),
+                                                C.byref(s), C.byref(m)), "apd_eval_masked_stats_host")
+    return {"count": c.value, "sum": s.value, "median": m.value}
+
+
 class EvalEngine:
     """One apd_eval_ctx (include/apd_eval.h): truncated nearest-neighbour distances to a target cloud,
     voxel down-sampling, z-buffer rendering and visibility, free gaps and voxel scores, crop volume,
-    nearest neighbour with index, transform and ICP registration. Clouds are (n, 3) float32: numpy arrays (results come back as numpy) or
+    nearest neighbour with index, transform and ICP registration, radius thinning, observability mask,
+    half-space and masked statistics. Clouds are (n, 3) float32: numpy arrays (results come back as numpy) or
     torch tensors on the context's device (results come back as tensors there; torch's current
     stream is waited for first, as for every device input of this library)."""
 
@@ -957,6 +1073,103 @@ class EvalEngine:
                                                           C.byref(c), C.byref(t)), "apd_eval_get_register_timing")
         return {"eval_ms": e.value, "fold_ms": f.value, "solve_ms": s.value, "evaluations": k.value,
                 "crop_ms": c.value, "transform_ms": t.value}
+
+    # ---- radius thinning, observability mask, half-space, masked statistics ----
+
+    def radius_thin(self, xyz, radius: float, rank=None):
+        """Ascending int32 indices of the greedy radius thinning (apd_eval_radius_thin): visiting the
+        points in ascending (rank, index), a point is kept iff no point kept before it lies within
+        radius. rank: uint32 per point (a torch tensor: int32 holding the same bits), None = all equal."""
+        a, n, addr, dev = self._cloud(xyz)
+        if rank is not None and hasattr(rank, "data_ptr"):
+            r = rank.contiguous().reshape(-1)
+            if r.element_size() != 4 or r.numel() != n:
+                raise ValueError("rank holds one 32-bit word per point")
+            _torch_device_sync(r)
+            rptr = r.data_ptr() if n else None
+        else:
+            r = _host_rank(rank, n)
+            rptr = r.ctypes.data if (r is not None and n) else None
+        if dev:
+            import torch
+            keep = torch.empty(max(n, 1), dtype=torch.int32, device=a.device)
+            _torch_device_sync(a, keep)
+            kptr = keep.data_ptr()
+        else:
+            keep = np.empty(max(n, 1), np.int32)
+            kptr = keep.ctypes.data
+        n_keep = C.c_int64(0)
+        self._check(self.lib.apd_eval_radius_thin(self.ctx, n, addr, radius, rptr, kptr, C.addressof(n_keep)),
+                    "apd_eval_radius_thin")
+        return keep[:n_keep.value]
+
+    def thin_timing(self) -> dict:
+        s, r, k = C.c_double(), C.c_double(), C.c_int32()
+        self._check(self.lib.apd_eval_get_thin_timing(self.ctx, C.byref(s), C.byref(r), C.byref(k)),
+                    "apd_eval_get_thin_timing")
+        return {"sort_ms": s.value, "rounds_ms": r.value, "rounds": k.value}
+
+    def _flags_out(self, a, n: int, dev: bool):
+        if dev:
+            import torch
+            out = torch.zeros(n, dtype=torch.uint8, device=a.device)
+            _torch_device_sync(a, out)
+            return out, (out.data_ptr() if n else None)
+        out = np.zeros(n, np.uint8)
+        return out, (out.ctypes.data if n else None)
+
+    def obs_mask(self, xyz, mask, origin, res: float):
+        """uint8[n]: 1 where round((x - origin) / res + 1) indexes a set cell of the 3-D array `mask`
+        (apd_eval_obs_mask). The flattened mask is kept, here and on the device, while the same array
+        object is given."""
+        a, n, addr, dev = self._cloud(xyz)
+        if getattr(self, "_mask_obj", None) is not mask:
+            # the new bytes are made while the old ones are still alive, so they get another address
+            # and the library, which knows a mask by its address and dims, uploads them
+            flat, dims, _ = _mask_geometry(mask, origin)
+            self._mask_obj, self._mask_flat, self._mask_dims = mask, flat, dims
+        org = np.ascontiguousarray(origin, np.float64).reshape(-1)
+        if org.size != 3:
+            raise ValueError("origin is three doubles")
+        inside, iptr = self._flags_out(a, n, dev)
+        self._check(self.lib.apd_eval_obs_mask(self.ctx, n, addr, self._mask_dims.ctypes.data, org.ctypes.data,
+                                               float(res), self._mask_flat.ctypes.data, iptr), "apd_eval_obs_mask")
+        return inside
+
+    def half_space(self, xyz, plane):
+        """uint8[n]: 1 where P0 x + P1 y + P2 z + P3 > 0 in double (apd_eval_half_space)."""
+        a, n, addr, dev = self._cloud(xyz)
+        P = np.ascontiguousarray(plane, np.float64).reshape(-1)
+        if P.size != 4:
+            raise ValueError("a plane is four doubles")
+        above, aptr = self._flags_out(a, n, dev)
+        self._check(self.lib.apd_eval_half_space(self.ctx, n, addr, P.ctypes.data, aptr), "apd_eval_half_space")
+        return above
+
+    def masked_stats(self, dist, flag, limit: float) -> dict:
+        """{"count", "sum", "median"} of the distances with flag set (None: all) that are <= limit
+        (apd_eval_masked_stats); dist float32[n] and flag uint8[n] as numpy arrays or device tensors."""
+        d = _keep(dist, np.float32).reshape(-1)
+        f = None if flag is None else _keep(flag, np.uint8).reshape(-1)
+        n = int(d.shape[0])
+        if f is not None and int(f.shape[0]) != n:
+            raise ValueError("flag holds one byte per distance")
+        _torch_device_sync(d, f)
+
+        def addr(t):
+            if t is None or n == 0:
+                return None
+            return t.data_ptr() if hasattr(t, "data_ptr") else t.ctypes.data
+        c, s, m = C.c_int64(0), C.c_double(0.0), C.c_double(0.0)
+        self._check(self.lib.apd_eval_masked_stats(self.ctx, n, addr(d), addr(f), limit, C.byref(c), C.byref(s),
+                                                   C.byref(m)), "apd_eval_masked_stats")
+        return {"count": c.value, "sum": s.value, "median": m.value}
+
+    def dtu_timing(self) -> dict:
+        m, h, s = C.c_double(), C.c_double(), C.c_double()
+        self._check(self.lib.apd_eval_get_dtu_timing(self.ctx, C.byref(m), C.byref(h), C.byref(s)),
+                    "apd_eval_get_dtu_timing")
+        return {"mask_ms": m.value, "half_space_ms": h.value, "stats_ms": s.value}
 
     def close(self):
         if self.ctx:
@@ -1356,6 +1569,59 @@ def cloud_metrics_scanners(rec_xyz, scans, tolerances=ETH3D_TOLERANCES, voxel: f
         out["completeness_dist"] = side("completeness", G, R, None)
         out["f1"] = [2 * a * c / (a + c) if a + c > 0 else 0.0
                      for a, c in zip(out["accuracy"]["score"], out["completeness"]["score"])]
+    finally:
+        if engine is None:
+            eng.close()
+    return out
+
+
+def cloud_metrics_dtu(rec_xyz, gt_xyz, mask, bb, res: float, plane, density: float = 0.2, max_dist: float = 20.0,
+                      seed: int = 0, thin: bool = True, engine: Optional[EvalEngine] = None) -> dict:
+    """Accuracy and completeness of a reconstructed cloud under the DTU protocol, the `apd_eval --dtu_gt`
+    mode's sequence of calls. mask: the 3-D observability volume (ObsMask), bb: its bounding box (2, 3)
+    with the minimum in row 0 (BB), res: its cell size (Res), plane: the table plane (P, 4 values).
+
+    1. Unless thin is False the reconstruction is thinned to a minimum spacing of `density`: in ascending
+       (Philox rank drawn from `seed`, index) a point is kept iff no point kept before it lies within
+       `density` (EvalEngine.radius_thin; exact, the order is the only random element).
+    2. Distances thinned reconstruction -> ground truth and back, truncated at max_dist.
+    3. Accuracy: the thinned points whose cell round((p - bb[0]) / res + 1) lies in the mask and is set;
+       completeness: the ground-truth points with [p 1] . plane > 0. Both take the distances
+       <= nextafter(max_dist, 0) (MATLAB's strict <) and give their mean and median.
+
+    Modelled on the DTU MATLAB evaluation, not that code: a seeded order instead of randperm (reproducible,
+    but not MATLAB's numbers for any seed), doubles for the mask index, no chunks. Parity is not pinned."""
+    eng = engine or EvalEngine()
+    out = {"density": float(np.float32(density)), "max_dist": float(np.float32(max_dist)), "seed": int(seed),
+           "thinned": bool(thin), "timing_ms": {}}
+    try:
+        rec = np.ascontiguousarray(rec_xyz, np.float32).reshape(-1, 3)
+        gt = np.ascontiguousarray(gt_xyz, np.float32).reshape(-1, 3)
+        box = np.ascontiguousarray(bb, np.float64).reshape(2, 3)
+        if thin:
+            keep = eng.radius_thin(rec, density, dtu_ranks(len(rec), seed, eng.lib))
+            out["timing_ms"]["thin"] = eng.thin_timing()
+            data = np.ascontiguousarray(rec[keep])
+        else:
+            keep, data = np.arange(len(rec), dtype=np.int32), rec
+        limit = float(np.nextafter(np.float32(max_dist), np.float32(0)))
+        eng.set_target(gt)
+        d_acc, _ = eng.distances(data, max_dist)
+        eng.set_target(data)
+        d_comp, _ = eng.distances(gt, max_dist)
+        inside = eng.obs_mask(data, mask, box[0], res)
+        above = eng.half_space(gt, plane)
+        sa, sc = eng.masked_stats(d_acc, inside, limit), eng.masked_stats(d_comp, above, limit)
+        out["timing_ms"]["dtu"] = eng.dtu_timing()
+        out.update({"input_points": int(len(rec)), "thinned_points": int(len(data)),
+                    "in_mask_points": int(inside.sum()), "gt_points": int(len(gt)),
+                    "gt_above_plane_points": int(above.sum()), "accuracy_selected": sa["count"],
+                    "completeness_selected": sc["count"],
+                    "accuracy_mean": sa["sum"] / sa["count"] if sa["count"] else 0.0, "accuracy_median": sa["median"],
+                    "completeness_mean": sc["sum"] / sc["count"] if sc["count"] else 0.0,
+                    "completeness_median": sc["median"], "keep_idx": keep, "accuracy_dist": d_acc,
+                    "completeness_dist": d_comp, "inside": inside, "above": above})
+        out["overall"] = (out["accuracy_mean"] + out["completeness_mean"]) / 2.0
     finally:
         if engine is None:
             eng.close()

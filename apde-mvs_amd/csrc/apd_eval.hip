@@ -3,7 +3,10 @@
 // cloud into cameras with a per-point visibility count (integer atomics: deterministic), the
 // free-space gap of points against depth maps and per-voxel good / bad scores (integer sums); a crop
 // volume, the nearest neighbour with its index, and point-to-point ICP whose per-iteration sums are
-// taken in a fixed tree order in fp64 (the same bits every run, and the host twins' bits).
+// taken in a fixed tree order in fp64 (the same bits every run, and the host twins' bits); exact
+// radius thinning (the greedy maximal independent set of the radius graph as the fixed point of two
+// final rules over a shrinking worklist), an observability mask, a half-space and masked mean /
+// median statistics, the steps of the DTU protocol.
 //
 // Search structure: a Morton-sorted implicit bounding-volume tree.
 //   - finite targets are quantised to 21 bits per axis over their bounding box (in double) and sorted
@@ -32,6 +35,7 @@
 #include <vector>
 
 #include "../../include/apd_eval.h"
+#include "apd_dtu.h"
 #include "apd_register.h"
 
 namespace {
@@ -735,6 +739,211 @@ __global__ void __launch_bounds__(BLOCK) k_transform(const float *__restrict__ x
     out[3 * (size_t)i + 2] = (float)p[2];
 }
 
+// ---- radius thinning, observability mask, half-space, masked statistics ------------------------------
+
+constexpr uint8_t THIN_UNDECIDED = 0, THIN_KEPT = 1, THIN_REMOVED = 2;
+constexpr int THIN_RUNS = 9;         // the (y, z) rows around a point's cell, three x cells each
+constexpr int THIN_BATCH = 8;        // rounds per read-back once the worklist is small
+constexpr int THIN_BATCH_BELOW = 32768;
+constexpr uint64_t CELL_MASK = 0x1FFFFFull;
+
+struct ThinGrid {
+    double cell;   // 2 * radius
+    double lo[3];  // lowest occupied cell per axis
+};
+
+// key = cz << 42 | cy << 21 | cx over the occupied cells (apd_dtu_cell; the caller has checked that
+// every span is below 2^21): x is the least significant field, so the three x-neighbour cells of a
+// (y, z) row are one contiguous run of the sorted array.
+__global__ void __launch_bounds__(BLOCK) k_thin_keys(const float *__restrict__ xyz, int n, const ThinGrid g,
+                                                     uint64_t *keys, int *idx, unsigned long long *n_finite) {
+    const int i = blockIdx.x * BLOCK + threadIdx.x;
+    bool fin = false;
+    if (i < n) {
+        const float x = xyz[3 * (size_t)i], y = xyz[3 * (size_t)i + 1], z = xyz[3 * (size_t)i + 2];
+        fin = finite3(x, y, z);
+        uint64_t k = KEY_NONE;
+        if (fin) {
+            const uint64_t cx = (uint64_t)(apd_dtu_cell(x, g.cell) - g.lo[0]) & CELL_MASK;
+            const uint64_t cy = (uint64_t)(apd_dtu_cell(y, g.cell) - g.lo[1]) & CELL_MASK;
+            const uint64_t cz = (uint64_t)(apd_dtu_cell(z, g.cell) - g.lo[2]) & CELL_MASK;
+            k = cz << 42 | cy << 21 | cx;
+        }
+        keys[i] = k;
+        idx[i] = i;
+    }
+    const unsigned long long m = __ballot(fin);
+    if ((threadIdx.x & 63) == 0 && m) atomicAdd(n_finite, (unsigned long long)__popcll(m));
+}
+
+// the finite points in cell order, the rank in w (the index half of the priority key is idx_s)
+__global__ void __launch_bounds__(BLOCK) k_thin_gather(const float *__restrict__ xyz,
+                                                       const uint32_t *__restrict__ rank,
+                                                       const int *__restrict__ idx_s, int nf, float4 *pts) {
+    const int p = blockIdx.x * BLOCK + threadIdx.x;
+    if (p >= nf) return;
+    const int i = idx_s[p];
+    const size_t s = 3 * (size_t)i;
+    pts[p] = make_float4(xyz[s], xyz[s + 1], xyz[s + 2], __uint_as_float(rank ? rank[i] : 0u));
+}
+
+// first position in keys[0, nf) whose key is >= k
+__device__ __forceinline__ int thin_lower_bound(const uint64_t *__restrict__ keys, int lo, int hi, uint64_t k) {
+    while (lo < hi) {
+        const int mid = lo + ((hi - lo) >> 1);
+        if (keys[mid] < k) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
+// The neighbourhood of the point at sorted position p: for each of the 9 (y, z) rows around its cell
+// the positions [begin, end) of the cells x - 1 .. x + 1, found once; runs[r * nf + p].
+__global__ void __launch_bounds__(BLOCK) k_thin_runs(const uint64_t *__restrict__ keys, int nf, int2 *runs) {
+    const int p = blockIdx.x * BLOCK + threadIdx.x;
+    if (p >= nf) return;
+    const uint64_t key = keys[p];
+    const int64_t cx = (int64_t)(key & CELL_MASK), cy = (int64_t)(key >> 21 & CELL_MASK), cz = (int64_t)(key >> 42);
+    const uint64_t x0 = (uint64_t)max(cx - 1, (int64_t)0), x1 = (uint64_t)min(cx + 1, (int64_t)CELL_MASK);
+    for (int r = 0; r < THIN_RUNS; ++r) {
+        const int64_t y = cy + r % 3 - 1, z = cz + r / 3 - 1;
+        int2 run = make_int2(0, 0);
+        if (y >= 0 && z >= 0 && y <= (int64_t)CELL_MASK && z <= (int64_t)CELL_MASK) {
+            const uint64_t row = (uint64_t)z << 42 | (uint64_t)y << 21;
+            run.x = thin_lower_bound(keys, 0, nf, row | x0);
+            run.y = thin_lower_bound(keys, run.x, nf, (row | x1) + 1);
+        }
+        runs[(size_t)r * nf + p] = run;
+    }
+}
+
+// One round over the worklist (list == nullptr: positions 0 .. *m_in - 1). Lane = point. A point is
+// REMOVED as soon as one close point with a lower key is KEPT, and KEPT as soon as every close point
+// with a lower key is REMOVED; both are final, so the state array is updated in place: a read of a
+// neighbour's byte that another lane is changing returns UNDECIDED or its final value, and a stale
+// UNDECIDED only leaves this point on the worklist for another round. The bytes are read and written
+// by relaxed agent-scope atomics (no ordering is needed, only that a byte is read whole).
+// The points still undecided are appended to `next` (one integer atomic per wave; their order there
+// does not enter the result), their number accumulates in *m_out.
+__global__ void __launch_bounds__(BLOCK) k_thin_round(const float4 *__restrict__ pts, const int *__restrict__ idx_s,
+                                                      const int2 *__restrict__ runs, int nf, float r2,
+                                                      const int *__restrict__ list, const unsigned int *m_in,
+                                                      uint8_t *state, int *next, unsigned int *m_out) {
+    const unsigned int t = blockIdx.x * BLOCK + threadIdx.x;
+    bool pending = false;
+    int p = 0;
+    if (t < *m_in) {
+        p = list ? list[t] : (int)t;
+        const float4 a = pts[p];
+        const uint32_t ra = __float_as_uint(a.w);
+        const int ia = idx_s[p];
+        uint8_t verdict = THIN_KEPT;
+        for (int r = 0; r < THIN_RUNS && verdict != THIN_REMOVED; ++r) {
+            const int2 run = runs[(size_t)r * nf + p];
+            for (int j = run.x; j < run.y; ++j) {
+                const float4 b = pts[j];
+                if (j == p || !apd_dtu_close(a.x, a.y, a.z, b.x, b.y, b.z, r2)) continue;
+                const uint32_t rb = __float_as_uint(b.w);
+                if (rb > ra || (rb == ra && idx_s[j] > ia)) continue;  // a higher key: no say over p
+                const uint8_t s = __hip_atomic_load(state + j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (s == THIN_KEPT) {
+                    verdict = THIN_REMOVED;
+                    break;
+                }
+                if (s == THIN_UNDECIDED) verdict = THIN_UNDECIDED;
+            }
+        }
+        if (verdict != THIN_UNDECIDED)
+            __hip_atomic_store(state + p, verdict, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        else
+            pending = true;
+    }
+    const unsigned long long m = __ballot(pending);
+    if (m) {  // wave-uniform
+        const int lane = threadIdx.x & 63;
+        unsigned int base = 0;
+        if (lane == 0) base = atomicAdd(m_out, (unsigned int)__popcll(m));
+        base = (unsigned int)__shfl((int)base, 0);
+        if (pending) next[base + (unsigned int)__popcll(m & ((1ull << lane) - 1ull))] = p;
+    }
+}
+
+__global__ void __launch_bounds__(BLOCK) k_thin_flags(const uint8_t *__restrict__ state, const int *__restrict__ idx_s,
+                                                      int nf, int *flag) {
+    const int p = blockIdx.x * BLOCK + threadIdx.x;
+    if (p >= nf) return;
+    if (state[p] == THIN_KEPT) flag[idx_s[p]] = 1;
+}
+
+__global__ void __launch_bounds__(BLOCK) k_obs_mask(const float *__restrict__ xyz, int n, const apd_dtu_mask_geom g,
+                                                    const uint8_t *__restrict__ mask, uint8_t *inside) {
+    const int i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= n) return;
+    inside[i] = apd_dtu_inside(g, mask, xyz[3 * (size_t)i], xyz[3 * (size_t)i + 1], xyz[3 * (size_t)i + 2]) ? 1 : 0;
+}
+
+struct Plane4 {
+    double P[4];
+};
+__global__ void __launch_bounds__(BLOCK) k_half_space(const float *__restrict__ xyz, int n, const Plane4 pl,
+                                                      uint8_t *above) {
+    const int i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= n) return;
+    above[i] = apd_dtu_above(pl.P, xyz[3 * (size_t)i], xyz[3 * (size_t)i + 1], xyz[3 * (size_t)i + 2]) ? 1 : 0;
+}
+
+// The selection, its count, the sort keys and the block sums of the masked statistics. A workgroup
+// owns APD_REG_BLOCK consecutive indices in four passes, as k_reg_eval does, with one term per index:
+// the butterfly over a wave, the wave sums parked in index order, the same tree over the 16 slots.
+// keys[i] = the ordered image of a selected distance, else 0xFFFFFFFF (the image of no selected value:
+// only a NaN maps there), so the selected values are the first `count` entries of the sorted keys.
+__global__ void __launch_bounds__(BLOCK) k_stats_block(const float *__restrict__ dist,
+                                                       const uint8_t *__restrict__ flag, int n, float limit,
+                                                       double *__restrict__ partials, uint32_t *keys,
+                                                       unsigned long long *count) {
+    __shared__ double slot[REG_SLOTS];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int pass = 0; pass < APD_REG_BLOCK / BLOCK; ++pass) {
+        const int64_t i = (int64_t)blockIdx.x * APD_REG_BLOCK + pass * BLOCK + threadIdx.x;
+        bool sel = false;
+        double a = 0.0;
+        if (i < n) {
+            const float d = dist[i];
+            sel = apd_dtu_selected(d, !flag || flag[i] != 0, limit);
+            if (sel) a = (double)d;
+            keys[i] = sel ? apd_dtu_ord(d) : 0xFFFFFFFFu;
+        }
+        for (int s = 1; s < 64; s <<= 1) a += __shfl_xor(a, s);
+        const unsigned long long m = __ballot(sel);
+        if (lane == 0) {
+            slot[pass * (BLOCK / 64) + wave] = a;
+            if (m) atomicAdd(count, (unsigned long long)__popcll(m));
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double a[REG_SLOTS];
+        for (int w = 0; w < REG_SLOTS; ++w) a[w] = slot[w];
+        for (int w = REG_SLOTS; w > 1; w >>= 1)
+            for (int j = 0; j < w / 2; ++j) a[j] = a[2 * j] + a[2 * j + 1];
+        partials[blockIdx.x] = a[0];
+    }
+}
+
+// the block sums left to right from block 0's sum; no block: +0.0
+__global__ void __launch_bounds__(64) k_stats_fold(const double *__restrict__ partials, int nblocks, double *out) {
+    if (threadIdx.x != 0) return;
+    double s = 0.0;
+    if (nblocks > 0) s = partials[0];
+    int b = 1;
+    for (; b + 8 <= nblocks; b += 8) {
+        double v[8];
+        for (int k = 0; k < 8; ++k) v[k] = partials[b + k];
+        for (int k = 0; k < 8; ++k) s += v[k];
+    }
+    for (; b < nblocks; ++b) s += partials[b];
+    out[0] = s;
+}
+
 struct Buf {
     void *p = nullptr;
     size_t bytes = 0;
@@ -773,6 +982,17 @@ struct apd_eval_ctx {
     hipEvent_t ev2 = nullptr;
     double reg_eval_ms = 0.0, reg_fold_ms = 0.0, reg_solve_ms = 0.0, crop_ms = 0.0, transform_ms = 0.0;
     int reg_evaluations = 0;
+    // radius thinning: the points in cell order with their ranks, the 9 neighbour runs of every point,
+    // a byte of state each, the two worklists, the uploaded ranks and the per-round counters
+    Buf th_pts, th_runs, th_state, th_list0, th_list1, th_rank, th_small;
+    double thin_sort_ms = 0.0, thin_rounds_ms = 0.0;
+    int thin_rounds = 0;
+    // observability mask (kept while the caller gives the same pointer and dims), the flags of a call,
+    // the statistics' block sums and results
+    Buf m_mask, d_flag, st_part, st_out;
+    const void *mask_src = nullptr;
+    int32_t mask_dims[3] = {0, 0, 0};
+    double mask_ms = 0.0, half_space_ms = 0.0, stats_ms = 0.0;
 };
 
 #define EV_OK(ctx, call)                                                                           \
@@ -908,7 +1128,8 @@ void apd_eval_destroy(apd_eval_ctx *ctx) {
                    &ctx->q_xyz, &ctx->q_keys, &ctx->q_keys_s, &ctx->q_idx, &ctx->q_idx_s, &ctx->q_dist, &ctx->q_aux,
                    &ctx->sort_tmp, &ctx->small, &ctx->r_keys, &ctx->r_depth, &ctx->r_index, &ctx->r_small, &ctx->s_dist,
                    &ctx->s_gap, &ctx->s_cnt, &ctx->s_out, &ctx->c_poly, &ctx->x_out, &ctx->g_part, &ctx->g_sums,
-                   &ctx->n_idx})
+                   &ctx->n_idx, &ctx->th_pts, &ctx->th_runs, &ctx->th_state, &ctx->th_list0, &ctx->th_list1,
+                   &ctx->th_rank, &ctx->th_small, &ctx->m_mask, &ctx->d_flag, &ctx->st_part, &ctx->st_out})
         if (b->p) (void)hipFree(b->p);
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
     if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
@@ -1718,6 +1939,321 @@ int32_t apd_eval_get_register_timing(apd_eval_ctx *ctx, double *eval_ms, double 
     if (evaluations) *evaluations = ctx->reg_evaluations;
     if (crop_ms) *crop_ms = ctx->crop_ms;
     if (transform_ms) *transform_ms = ctx->transform_ms;
+    return APD_OK;
+}
+
+// ---- radius thinning, observability mask, half-space, masked statistics ------------------------------
+
+int32_t apd_eval_radius_thin(apd_eval_ctx *ctx, int64_t n64, const float *xyz, float radius, const uint32_t *rank,
+                             int32_t *keep_idx, int64_t *n_keep) {
+    if (!ctx) return APD_EINVAL;
+    int st = check_n(ctx, "apd_eval_radius_thin", n64, xyz);
+    if (st) return st;
+    float r2;
+    ThinGrid g{};
+    if (!apd_dtu_radius(radius, &r2, &g.cell)) {
+        ctx->err = "apd_eval_radius_thin: radius must be positive with a finite, normal fp32 square";
+        return APD_EINVAL;
+    }
+    if (!n_keep || (n64 > 0 && !keep_idx)) {
+        ctx->err = "apd_eval_radius_thin: NULL output";
+        return APD_EINVAL;
+    }
+    EV_OK(ctx, hipSetDevice(ctx->device));
+    const int n = (int)n64;
+    ctx->thin_sort_ms = ctx->thin_rounds_ms = 0.0;
+    ctx->thin_rounds = 0;
+    unsigned long long kept = 0;
+    if (n == 0) {
+        EV_OK(ctx, hipMemcpy(n_keep, &kept, 8, hipMemcpyDefault));
+        return APD_OK;
+    }
+    // q_dist holds the kept flags, q_aux their exclusive scan from byte 128 and the kept count at byte
+    // 64, q_keys (free once sorted) the kept indices: the layout of apd_eval_voxel_downsample.
+    // th_small: the bounds at byte 0, the finite count at byte 64, the round counters from byte 128.
+    if ((st = grow(ctx, ctx->q_xyz, (size_t)n * 12)) || (st = grow(ctx, ctx->q_keys, (size_t)n * 8)) ||
+        (st = grow(ctx, ctx->q_keys_s, (size_t)n * 8)) || (st = grow(ctx, ctx->q_idx, (size_t)n * 4)) ||
+        (st = grow(ctx, ctx->q_idx_s, (size_t)n * 4)) || (st = grow(ctx, ctx->q_dist, (size_t)n * 4)) ||
+        (st = grow(ctx, ctx->q_aux, 128 + (size_t)n * 4)) || (st = grow(ctx, ctx->th_small, 256)) ||
+        (rank && (st = grow(ctx, ctx->th_rank, (size_t)n * 4))))
+        return st;
+    uint32_t *bounds = (uint32_t *)ctx->th_small.p;
+    unsigned long long *n_finite = (unsigned long long *)((char *)ctx->th_small.p + 64);
+    unsigned int *cnt = (unsigned int *)((char *)ctx->th_small.p + 128);  // THIN_BATCH + 1 words
+    unsigned long long *counter = (unsigned long long *)((char *)ctx->q_aux.p + 64);
+    hipStream_t s = ctx->stream;
+    EV_OK(ctx, hipMemcpyAsync(ctx->q_xyz.p, xyz, (size_t)n * 12, hipMemcpyDefault, s));
+    if (rank) EV_OK(ctx, hipMemcpyAsync(ctx->th_rank.p, rank, (size_t)n * 4, hipMemcpyDefault, s));
+    EV_OK(ctx, hipEventRecord(ctx->ev0, s));
+    EV_OK(ctx, hipMemsetAsync(bounds, 0xFF, 12, s));
+    EV_OK(ctx, hipMemsetAsync(bounds + 3, 0, 12, s));
+    EV_OK(ctx, hipMemsetAsync(n_finite, 0, 8, s));
+    hipLaunchKernelGGL(k_bounds, dim3(grid_capped(n)), dim3(BLOCK), 0, s, (const float *)ctx->q_xyz.p, n, bounds);
+    EV_OK(ctx, hipGetLastError());
+    uint32_t hb[6];
+    EV_OK(ctx, hipMemcpyAsync(hb, bounds, 24, hipMemcpyDeviceToHost, s));
+    EV_OK(ctx, hipStreamSynchronize(s));
+    if (hb[0] == 0xFFFFFFFFu) {  // no finite point
+        EV_OK(ctx, hipMemcpy(n_keep, &kept, 8, hipMemcpyDefault));
+        return APD_OK;
+    }
+    // the cell index is monotone in the coordinate, so the occupied cells span cell(min) .. cell(max)
+    for (int a = 0; a < 3; ++a) {
+        auto dec = [](uint32_t u) {
+            const uint32_t b = (u & 0x80000000u) ? (u & 0x7FFFFFFFu) : ~u;
+            float f;
+            memcpy(&f, &b, 4);
+            return f;
+        };
+        g.lo[a] = apd_dtu_cell(dec(hb[a]), g.cell);
+        if (!(apd_dtu_cell(dec(hb[3 + a]), g.cell) - g.lo[a] < APD_DTU_CELL_SPAN)) {
+            ctx->err = "apd_eval_radius_thin: an axis spans more than 2^21 cells";
+            return APD_EINVAL;
+        }
+    }
+    hipLaunchKernelGGL(k_thin_keys, dim3(grid_for(n)), dim3(BLOCK), 0, s, (const float *)ctx->q_xyz.p, n, g,
+                       (uint64_t *)ctx->q_keys.p, (int *)ctx->q_idx.p, n_finite);
+    EV_OK(ctx, hipGetLastError());
+    if ((st = sort_pairs(ctx, ctx->q_keys, ctx->q_keys_s, ctx->q_idx, ctx->q_idx_s, n))) return st;
+    unsigned long long nf64 = 0;
+    EV_OK(ctx, hipMemcpyAsync(&nf64, n_finite, 8, hipMemcpyDeviceToHost, s));
+    EV_OK(ctx, hipStreamSynchronize(s));
+    const int nf = (int)nf64;  // >= 1: the bounds saw a finite point
+    if ((st = grow(ctx, ctx->th_pts, (size_t)nf * 16)) ||
+        (st = grow(ctx, ctx->th_runs, (size_t)nf * THIN_RUNS * sizeof(int2))) ||
+        (st = grow(ctx, ctx->th_state, (size_t)nf)) || (st = grow(ctx, ctx->th_list0, (size_t)nf * 4)) ||
+        (st = grow(ctx, ctx->th_list1, (size_t)nf * 4)))
+        return st;
+    const float4 *pts = (const float4 *)ctx->th_pts.p;
+    const int *idx_s = (const int *)ctx->q_idx_s.p;
+    const int2 *runs = (const int2 *)ctx->th_runs.p;
+    uint8_t *state = (uint8_t *)ctx->th_state.p;
+    int *lists[2] = {(int *)ctx->th_list0.p, (int *)ctx->th_list1.p};
+    hipLaunchKernelGGL(k_thin_gather, dim3(grid_for(nf)), dim3(BLOCK), 0, s, (const float *)ctx->q_xyz.p,
+                       rank ? (const uint32_t *)ctx->th_rank.p : (const uint32_t *)nullptr, idx_s, nf,
+                       (float4 *)ctx->th_pts.p);
+    hipLaunchKernelGGL(k_thin_runs, dim3(grid_for(nf)), dim3(BLOCK), 0, s, (const uint64_t *)ctx->q_keys_s.p, nf,
+                       (int2 *)ctx->th_runs.p);
+    EV_OK(ctx, hipMemsetAsync(state, THIN_UNDECIDED, (size_t)nf, s));
+    EV_OK(ctx, hipGetLastError());
+    EV_OK(ctx, hipEventRecord(ctx->ev1, s));
+
+    // Rounds until no point is undecided. Round r reads the worklist lists[r & 1] (round 0: every
+    // position) and writes lists[(r + 1) & 1]; a batch of rounds shares one read-back of its counters,
+    // each round's grid sized by the count at the start of the batch (the counts only fall). Every
+    // round decides at least the lowest-key undecided point, so m reaches 0.
+    unsigned int m = (unsigned int)nf;
+    int round = 0;
+    while (m > 0) {
+        const int batch = (int)m > THIN_BATCH_BELOW ? 1 : THIN_BATCH;
+        EV_OK(ctx, hipMemsetD32Async((hipDeviceptr_t)cnt, (int)m, 1, s));
+        EV_OK(ctx, hipMemsetAsync(cnt + 1, 0, (size_t)batch * 4, s));
+        for (int k = 0; k < batch; ++k, ++round)
+            hipLaunchKernelGGL(k_thin_round, dim3(grid_for(m)), dim3(BLOCK), 0, s, pts, idx_s, runs, nf, r2,
+                               round == 0 ? (const int *)nullptr : (const int *)lists[round & 1],
+                               (const unsigned int *)(cnt + k), state, lists[(round + 1) & 1], cnt + k + 1);
+        EV_OK(ctx, hipGetLastError());
+        unsigned int hc[THIN_BATCH];
+        EV_OK(ctx, hipMemcpyAsync(hc, cnt + 1, (size_t)batch * 4, hipMemcpyDeviceToHost, s));
+        EV_OK(ctx, hipStreamSynchronize(s));
+        int used = batch;  // the rounds of this batch up to the first that left nothing
+        for (int k = 0; k < batch; ++k)
+            if (hc[k] == 0) {
+                used = k + 1;
+                break;
+            }
+        ctx->thin_rounds += used;
+        if (hc[batch - 1] >= m) {  // cannot happen: a round decides at least one point
+            ctx->err = "apd_eval_radius_thin: a round decided nothing";
+            return APD_EDEVICE;
+        }
+        m = hc[batch - 1];
+    }
+
+    int *flag = (int *)ctx->q_dist.p, *pos = (int *)ctx->q_aux.p + 32, *keep = (int *)ctx->q_keys.p;
+    EV_OK(ctx, hipMemsetAsync(flag, 0, (size_t)n * 4, s));
+    hipLaunchKernelGGL(k_thin_flags, dim3(grid_for(nf)), dim3(BLOCK), 0, s, (const uint8_t *)state, idx_s, nf, flag);
+    EV_OK(ctx, hipGetLastError());
+    size_t tb = 0;
+    EV_OK(ctx, rocprim::exclusive_scan(nullptr, tb, flag, pos, 0, (size_t)n, rocprim::plus<int>(), s));
+    if ((st = grow(ctx, ctx->sort_tmp, tb))) return st;
+    EV_OK(ctx, rocprim::exclusive_scan(ctx->sort_tmp.p, tb, flag, pos, 0, (size_t)n, rocprim::plus<int>(), s));
+    hipLaunchKernelGGL(k_voxel_compact, dim3(grid_for(n)), dim3(BLOCK), 0, s, (const int *)flag, (const int *)pos, n,
+                       keep, counter);
+    EV_OK(ctx, hipGetLastError());
+    EV_OK(ctx, hipEventRecord(ctx->ev2, s));
+    EV_OK(ctx, hipMemcpyAsync(&kept, counter, 8, hipMemcpyDeviceToHost, s));
+    EV_OK(ctx, hipStreamSynchronize(s));
+    if (kept > 0) EV_OK(ctx, hipMemcpy(keep_idx, keep, (size_t)kept * 4, hipMemcpyDefault));
+    EV_OK(ctx, hipMemcpy(n_keep, &kept, 8, hipMemcpyDefault));
+    float f = 0.0f;
+    EV_OK(ctx, hipEventElapsedTime(&f, ctx->ev0, ctx->ev1));
+    ctx->thin_sort_ms = (double)f;
+    EV_OK(ctx, hipEventElapsedTime(&f, ctx->ev1, ctx->ev2));
+    ctx->thin_rounds_ms = (double)f;
+    return APD_OK;
+}
+
+int32_t apd_eval_get_thin_timing(apd_eval_ctx *ctx, double *sort_ms, double *rounds_ms, int32_t *rounds) {
+    if (!ctx) return APD_EINVAL;
+    if (sort_ms) *sort_ms = ctx->thin_sort_ms;
+    if (rounds_ms) *rounds_ms = ctx->thin_rounds_ms;
+    if (rounds) *rounds = ctx->thin_rounds;
+    return APD_OK;
+}
+
+int32_t apd_eval_obs_mask(apd_eval_ctx *ctx, int64_t n64, const float *xyz, const int32_t dims[3],
+                          const double origin[3], double res, const uint8_t *mask, uint8_t *inside) {
+    if (!ctx) return APD_EINVAL;
+    int st = check_n(ctx, "apd_eval_obs_mask", n64, xyz);
+    if (st) return st;
+    if (!dims || !origin || !mask || (n64 > 0 && !inside)) {
+        ctx->err = "apd_eval_obs_mask: NULL dims, origin, mask or output";
+        return APD_EINVAL;
+    }
+    apd_dtu_mask_geom g;
+    double total = 1.0;
+    for (int k = 0; k < 3; ++k) {
+        if (dims[k] < 1 || !std::isfinite(origin[k])) {
+            ctx->err = "apd_eval_obs_mask: a dim below 1 or a non-finite origin";
+            return APD_EINVAL;
+        }
+        g.dims[k] = dims[k];
+        g.origin[k] = origin[k];
+        total *= (double)dims[k];
+    }
+    if (total > 2147483648.0) {
+        ctx->err = "apd_eval_obs_mask: the mask has more than 2^31 cells";
+        return APD_EINVAL;
+    }
+    if (!(res > 0.0) || !std::isfinite(res)) {
+        ctx->err = "apd_eval_obs_mask: res must be positive and finite";
+        return APD_EINVAL;
+    }
+    g.res = res;
+    EV_OK(ctx, hipSetDevice(ctx->device));
+    const int n = (int)n64;
+    ctx->mask_ms = 0.0;
+    hipStream_t s = ctx->stream;
+    if (ctx->mask_src != mask || memcmp(ctx->mask_dims, dims, 12) != 0) {
+        ctx->mask_src = nullptr;
+        if ((st = grow(ctx, ctx->m_mask, (size_t)total))) return st;
+        EV_OK(ctx, hipMemcpyAsync(ctx->m_mask.p, mask, (size_t)total, hipMemcpyDefault, s));
+        EV_OK(ctx, hipStreamSynchronize(s));
+        ctx->mask_src = mask;
+        memcpy(ctx->mask_dims, dims, 12);
+    }
+    if (n == 0) return APD_OK;
+    if ((st = grow(ctx, ctx->q_xyz, (size_t)n * 12)) || (st = grow(ctx, ctx->d_flag, (size_t)n))) return st;
+    EV_OK(ctx, hipMemcpyAsync(ctx->q_xyz.p, xyz, (size_t)n * 12, hipMemcpyDefault, s));
+    EV_OK(ctx, hipEventRecord(ctx->ev0, s));
+    hipLaunchKernelGGL(k_obs_mask, dim3(grid_for(n)), dim3(BLOCK), 0, s, (const float *)ctx->q_xyz.p, n, g,
+                       (const uint8_t *)ctx->m_mask.p, (uint8_t *)ctx->d_flag.p);
+    EV_OK(ctx, hipGetLastError());
+    EV_OK(ctx, hipEventRecord(ctx->ev1, s));
+    EV_OK(ctx, hipMemcpyAsync(inside, ctx->d_flag.p, (size_t)n, hipMemcpyDefault, s));
+    EV_OK(ctx, hipStreamSynchronize(s));
+    return elapsed(ctx, ctx->mask_ms);
+}
+
+int32_t apd_eval_half_space(apd_eval_ctx *ctx, int64_t n64, const float *xyz, const double P[4], uint8_t *above) {
+    if (!ctx) return APD_EINVAL;
+    int st = check_n(ctx, "apd_eval_half_space", n64, xyz);
+    if (st) return st;
+    if (!P || (n64 > 0 && !above)) {
+        ctx->err = "apd_eval_half_space: NULL plane or output";
+        return APD_EINVAL;
+    }
+    const int n = (int)n64;
+    ctx->half_space_ms = 0.0;
+    if (n == 0) return APD_OK;
+    EV_OK(ctx, hipSetDevice(ctx->device));
+    if ((st = grow(ctx, ctx->q_xyz, (size_t)n * 12)) || (st = grow(ctx, ctx->d_flag, (size_t)n))) return st;
+    Plane4 pl;
+    for (int k = 0; k < 4; ++k) pl.P[k] = P[k];
+    hipStream_t s = ctx->stream;
+    EV_OK(ctx, hipMemcpyAsync(ctx->q_xyz.p, xyz, (size_t)n * 12, hipMemcpyDefault, s));
+    EV_OK(ctx, hipEventRecord(ctx->ev0, s));
+    hipLaunchKernelGGL(k_half_space, dim3(grid_for(n)), dim3(BLOCK), 0, s, (const float *)ctx->q_xyz.p, n, pl,
+                       (uint8_t *)ctx->d_flag.p);
+    EV_OK(ctx, hipGetLastError());
+    EV_OK(ctx, hipEventRecord(ctx->ev1, s));
+    EV_OK(ctx, hipMemcpyAsync(above, ctx->d_flag.p, (size_t)n, hipMemcpyDefault, s));
+    EV_OK(ctx, hipStreamSynchronize(s));
+    return elapsed(ctx, ctx->half_space_ms);
+}
+
+int32_t apd_eval_masked_stats(apd_eval_ctx *ctx, int64_t n64, const float *dist, const uint8_t *flag, float limit,
+                              int64_t *count, double *sum, double *median) {
+    if (!ctx) return APD_EINVAL;
+    int st = check_n(ctx, "apd_eval_masked_stats", n64, dist);
+    if (st) return st;
+    if (limit != limit) {
+        ctx->err = "apd_eval_masked_stats: the limit is NaN";
+        return APD_EINVAL;
+    }
+    const int n = (int)n64;
+    ctx->stats_ms = 0.0;
+    if (count) *count = 0;
+    if (sum) *sum = 0.0;
+    if (median) *median = 0.0;
+    if (n == 0) return APD_OK;
+    EV_OK(ctx, hipSetDevice(ctx->device));
+    const int nblocks = (int)((n64 + APD_REG_BLOCK - 1) / APD_REG_BLOCK);
+    // s_dist: the distances; q_keys / q_keys_s: the 32-bit sort keys and their sorted copy;
+    // st_out: the sum at byte 0, the count at byte 8
+    if ((st = grow(ctx, ctx->s_dist, (size_t)n * 4)) || (flag && (st = grow(ctx, ctx->d_flag, (size_t)n))) ||
+        (st = grow(ctx, ctx->q_keys, (size_t)n * 8)) || (st = grow(ctx, ctx->q_keys_s, (size_t)n * 8)) ||
+        (st = grow(ctx, ctx->st_part, (size_t)nblocks * 8)) || (st = grow(ctx, ctx->st_out, 64)))
+        return st;
+    uint32_t *keys = (uint32_t *)ctx->q_keys.p, *keys_s = (uint32_t *)ctx->q_keys_s.p;
+    double *out = (double *)ctx->st_out.p;
+    unsigned long long *cnt = (unsigned long long *)ctx->st_out.p + 1;
+    hipStream_t s = ctx->stream;
+    EV_OK(ctx, hipMemcpyAsync(ctx->s_dist.p, dist, (size_t)n * 4, hipMemcpyDefault, s));
+    if (flag) EV_OK(ctx, hipMemcpyAsync(ctx->d_flag.p, flag, (size_t)n, hipMemcpyDefault, s));
+    EV_OK(ctx, hipEventRecord(ctx->ev0, s));
+    EV_OK(ctx, hipMemsetAsync(cnt, 0, 8, s));
+    hipLaunchKernelGGL(k_stats_block, dim3(nblocks), dim3(BLOCK), 0, s, (const float *)ctx->s_dist.p,
+                       flag ? (const uint8_t *)ctx->d_flag.p : (const uint8_t *)nullptr, n, limit,
+                       (double *)ctx->st_part.p, keys, cnt);
+    hipLaunchKernelGGL(k_stats_fold, dim3(1), dim3(64), 0, s, (const double *)ctx->st_part.p, nblocks, out);
+    EV_OK(ctx, hipGetLastError());
+    size_t tb = 0;
+    EV_OK(ctx, rocprim::radix_sort_keys(nullptr, tb, keys, keys_s, (size_t)n, 0, 32, s));
+    if ((st = grow(ctx, ctx->sort_tmp, tb))) return st;
+    EV_OK(ctx, rocprim::radix_sort_keys(ctx->sort_tmp.p, tb, keys, keys_s, (size_t)n, 0, 32, s));
+    EV_OK(ctx, hipEventRecord(ctx->ev1, s));
+    struct {
+        double sum;
+        unsigned long long count;
+    } h{};
+    EV_OK(ctx, hipMemcpyAsync(&h, ctx->st_out.p, 16, hipMemcpyDeviceToHost, s));
+    EV_OK(ctx, hipStreamSynchronize(s));
+    double med = 0.0;
+    if (h.count > 0) {
+        const size_t m = (size_t)h.count, a = (m - 1) / 2, b = m / 2;  // a == b for an odd count
+        uint32_t mid[2];
+        EV_OK(ctx, hipMemcpy(&mid[0], keys_s + a, 4, hipMemcpyDeviceToHost));
+        EV_OK(ctx, hipMemcpy(&mid[1], keys_s + b, 4, hipMemcpyDeviceToHost));
+        float v[2];
+        for (int k = 0; k < 2; ++k) {
+            const uint32_t u = (mid[k] & 0x80000000u) ? (mid[k] & 0x7FFFFFFFu) : ~mid[k];
+            memcpy(&v[k], &u, 4);
+        }
+        med = a == b ? (double)v[0] : ((double)v[0] + (double)v[1]) / 2.0;
+    }
+    if (count) *count = (int64_t)h.count;
+    if (sum) *sum = h.sum;
+    if (median) *median = med;
+    return elapsed(ctx, ctx->stats_ms);
+}
+
+int32_t apd_eval_get_dtu_timing(apd_eval_ctx *ctx, double *mask_ms, double *half_space_ms, double *stats_ms) {
+    if (!ctx) return APD_EINVAL;
+    if (mask_ms) *mask_ms = ctx->mask_ms;
+    if (half_space_ms) *half_space_ms = ctx->half_space_ms;
+    if (stats_ms) *stats_ms = ctx->stats_ms;
     return APD_OK;
 }
 

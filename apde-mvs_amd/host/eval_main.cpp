@@ -10,8 +10,12 @@
 // Tanks and Temples mode (--tat_gt) moves the reconstruction into the scan's frame, refines that by ICP
 // on the GPU, cuts both clouds to the scene's crop volume, thins both by voxel and reports precision,
 // recall and F-score at tau (modelled on the Tanks and Temples toolbox, not that toolbox).
+// DTU mode (--dtu_gt) thins the reconstruction to a minimum point spacing on the GPU, restricts accuracy
+// to the scan's observability mask and completeness to the points above the table plane, and reports
+// the mean and median distances (modelled on the DTU MATLAB evaluation, not that code).
 #include <algorithm>
 #include <atomic>
+#include <cerrno>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -111,6 +115,22 @@ const char *kHelp =
     "  understood of --tat_crop / --tat_trans / --init_trans and exits.\n"
     "  --tat_gt excludes every other mode.\n"
     "\n"
+    "DTU mode (uses the GPU):\n"
+    "  apd_eval --cloud REC.ply --dtu_gt stlNNN_total.ply --dtu_mask ObsMaskN_10.mat --dtu_plane PlaneN.mat\n"
+    "           [--dtu_density 0.2] [--dtu_max_dist 20] [--dtu_seed 0] [--dtu_no_thin]\n"
+    "           [--thinned_cloud_out FILE.ply] [--gpu_index G] [--json OUT.json]\n"
+    "  The mask file (Level-5 MAT, not -v7.3) supplies ObsMask, BB (2x3: min row, max row) and Res, the\n"
+    "  plane file P (4 values). 1. Unless --dtu_no_thin, REC is thinned to a minimum point spacing of the\n"
+    "  density: the points are visited in the order of a Philox rank drawn from --dtu_seed (ties by index)\n"
+    "  and a point is kept iff no point kept before it lies within the density (exact, on the GPU).\n"
+    "  2. Distances thinned REC -> GT and GT -> thinned REC, truncated at max_dist. 3. Accuracy takes the\n"
+    "  points of REC whose cell round((p - BB(1,:)) / Res + 1) lies inside ObsMask and is set, completeness\n"
+    "  the points of GT with [p 1] * P > 0; both take the distances < max_dist and report their mean and\n"
+    "  median; overall = (accuracy mean + completeness mean) / 2. --thinned_cloud_out writes the thinned REC.\n"
+    "  Modelled on the DTU MATLAB evaluation, NOT that code: a seeded order instead of randperm (the\n"
+    "  numbers are reproducible, but not MATLAB's for any seed), doubles for the mask index, no chunks.\n"
+    "  Parity is unpinned. --dtu_gt excludes every other mode.\n"
+    "\n"
     "The modes may be combined in one invocation; --json then holds all of them.\n"
     "Exit status: 0 ok, 1 run-time failure, 2 bad arguments or unreadable input.\n";
 
@@ -131,6 +151,11 @@ struct Options {
     float tau = 0.0f;
     bool tau_given = false, no_refine = false, no_scale = false, tat_dump = false, stages_given = false;
     std::vector<std::pair<float, float>> stages;  // (voxel, max_corr)
+    // DTU mode
+    std::string dtu_gt, dtu_mask, dtu_plane, thinned_out;
+    float dtu_density = 0.2f, dtu_max_dist = 20.0f;
+    uint32_t dtu_seed = 0;
+    bool dtu_no_thin = false, dtu_option_given = false;
 };
 
 bool parse_float(const std::string &s, float &v) {
@@ -915,6 +940,159 @@ int run_tat_dump(const TatInputs &in, bool have_crop) {
     return 0;
 }
 
+// ---- DTU mode ----------------------------------------------------------------------------------------
+
+struct DtuInputs {
+    std::vector<float> rec, gt;
+    std::vector<uint8_t> mask;  // column-major
+    int32_t dims[3] = {1, 1, 1};
+    double origin[3] = {0, 0, 0}, res = 0.0, plane[4] = {0, 0, 0, 0};
+};
+
+// ObsMask, BB and Res of the mask file, P of the plane file
+bool read_dtu_side_files(const Options &opt, DtuInputs &in, std::string &err) {
+    std::vector<MatArray> a;
+    if (!read_mat5(opt.dtu_mask, {{"ObsMask", true}, {"BB", false}, {"Res", false}}, a, err)) return false;
+    const MatArray &m = a[0], &bb = a[1], &res = a[2];
+    if (m.dims.size() < 2 || m.bytes.empty()) {
+        err = opt.dtu_mask + ": ObsMask is not a non-empty 2-D or 3-D array";
+        return false;
+    }
+    for (size_t k = 0; k < m.dims.size(); ++k) in.dims[k] = (int32_t)m.dims[k];  // each below 2^31 (read_mat5)
+    if (bb.dims.size() != 2 || bb.dims[0] != 2 || bb.dims[1] != 3 || res.values.size() != 1) {
+        err = opt.dtu_mask + ": BB is not 2x3 or Res is not a scalar";
+        return false;
+    }
+    for (int k = 0; k < 3; ++k) in.origin[k] = bb.values[(size_t)(2 * k)];  // row 0 of a column-major 2x3
+    in.res = res.values[0];
+    if (!std::isfinite(in.origin[0]) || !std::isfinite(in.origin[1]) || !std::isfinite(in.origin[2]) ||
+        !(in.res > 0.0) || !std::isfinite(in.res)) {
+        err = opt.dtu_mask + ": BB is not finite or Res is not positive and finite";
+        return false;
+    }
+    in.mask = std::move(a[0].bytes);
+    if (!read_mat5(opt.dtu_plane, {{"P", false}}, a, err)) return false;
+    if (a[0].values.size() != 4) {
+        err = opt.dtu_plane + ": P does not hold 4 values";
+        return false;
+    }
+    for (int k = 0; k < 4; ++k) {
+        in.plane[k] = a[0].values[(size_t)k];
+        if (!std::isfinite(in.plane[k])) {
+            err = opt.dtu_plane + ": P is not finite";
+            return false;
+        }
+    }
+    return true;
+}
+
+// returns the exit status; appends "dtu": {...} to json
+int run_dtu(const Options &opt, const DtuInputs &in, std::string &json) {
+    apd_eval_ctx *ctx = apd_eval_create(opt.gpu);
+    if (!ctx) {
+        std::fprintf(stderr, "apd_eval: %s (device %d)\n", apd_eval_last_error(nullptr), opt.gpu);
+        return 1;
+    }
+    const int64_t n_in = (int64_t)(in.rec.size() / 3), n_gt = (int64_t)(in.gt.size() / 3);
+    std::vector<float> data;
+    double sort_ms = 0.0, rounds_ms = 0.0, build_ms = 0.0, query_ms = 0.0, mask_ms = 0.0, plane_ms = 0.0, stats_ms = 0.0;
+    int32_t rounds = 0;
+    bool ok = true;
+    if (opt.dtu_no_thin) {
+        data = in.rec;
+    } else {
+        std::vector<uint32_t> rank((size_t)std::max<int64_t>(n_in, 1));
+        std::vector<int32_t> keep((size_t)std::max<int64_t>(n_in, 1));
+        int64_t nk = 0;
+        apd_eval_dtu_ranks(n_in, opt.dtu_seed, rank.data());
+        const int st = apd_eval_radius_thin(ctx, n_in, in.rec.data(), opt.dtu_density, rank.data(), keep.data(), &nk);
+        if (st != APD_OK) ok = fail_ctx(ctx, "apd_eval_radius_thin", st);
+        else {
+            apd_eval_get_thin_timing(ctx, &sort_ms, &rounds_ms, &rounds);
+            data = gather(in.rec, keep, nk);
+        }
+    }
+    const int64_t n_data = (int64_t)(data.size() / 3);
+    std::vector<float> d_acc((size_t)std::max<int64_t>(n_data, 1)), d_comp((size_t)std::max<int64_t>(n_gt, 1));
+    std::vector<uint8_t> inside((size_t)std::max<int64_t>(n_data, 1)), above((size_t)std::max<int64_t>(n_gt, 1));
+    auto side = [&](const std::vector<float> &q, const std::vector<float> &t, std::vector<float> &dist) {
+        int st = apd_eval_set_target(ctx, (int64_t)(t.size() / 3), t.data());
+        if (st != APD_OK) return fail_ctx(ctx, "apd_eval_set_target", st);
+        st = apd_eval_distances(ctx, (int64_t)(q.size() / 3), q.data(), opt.dtu_max_dist, dist.data(), 0, nullptr, nullptr);
+        if (st != APD_OK) return fail_ctx(ctx, "apd_eval_distances", st);
+        double b = 0.0, qm = 0.0;
+        apd_eval_get_timing(ctx, &b, &qm, nullptr);
+        build_ms += b;
+        query_ms += qm;
+        return true;
+    };
+    ok = ok && side(data, in.gt, d_acc) && side(in.gt, data, d_comp);
+    if (ok) {
+        int st = apd_eval_obs_mask(ctx, n_data, data.data(), in.dims, in.origin, in.res, in.mask.data(), inside.data());
+        if (st != APD_OK) ok = fail_ctx(ctx, "apd_eval_obs_mask", st);
+        else if ((st = apd_eval_half_space(ctx, n_gt, in.gt.data(), in.plane, above.data())) != APD_OK)
+            ok = fail_ctx(ctx, "apd_eval_half_space", st);
+        apd_eval_get_dtu_timing(ctx, &mask_ms, &plane_ms, nullptr);
+    }
+    // MATLAB's strict `< MaxDist`, as `<=` against the float below it
+    const float limit = std::nextafterf(opt.dtu_max_dist, 0.0f);
+    int64_t acc_n = 0, comp_n = 0;
+    double acc_sum = 0.0, acc_med = 0.0, comp_sum = 0.0, comp_med = 0.0;
+    if (ok) {
+        double ms = 0.0;
+        int st = apd_eval_masked_stats(ctx, n_data, d_acc.data(), inside.data(), limit, &acc_n, &acc_sum, &acc_med);
+        if (st != APD_OK) ok = fail_ctx(ctx, "apd_eval_masked_stats", st);
+        apd_eval_get_dtu_timing(ctx, nullptr, nullptr, &ms);
+        stats_ms += ms;
+        if (ok && (st = apd_eval_masked_stats(ctx, n_gt, d_comp.data(), above.data(), limit, &comp_n, &comp_sum,
+                                              &comp_med)) != APD_OK)
+            ok = fail_ctx(ctx, "apd_eval_masked_stats", st);
+        apd_eval_get_dtu_timing(ctx, nullptr, nullptr, &ms);
+        stats_ms += ms;
+    }
+    apd_eval_destroy(ctx);
+    if (ok && !opt.thinned_out.empty()) {
+        const std::vector<uint8_t> rgb(data.size(), 200);
+        if (!write_ply_xyz_rgb(opt.thinned_out, data, rgb)) {
+            std::fprintf(stderr, "apd_eval: cannot write %s\n", opt.thinned_out.c_str());
+            ok = false;
+        }
+    }
+    if (!ok) return 1;
+    int64_t n_inside = 0, n_above = 0;
+    for (int64_t i = 0; i < n_data; ++i) n_inside += inside[(size_t)i];
+    for (int64_t i = 0; i < n_gt; ++i) n_above += above[(size_t)i];
+    const double acc_mean = acc_n ? acc_sum / (double)acc_n : 0.0, comp_mean = comp_n ? comp_sum / (double)comp_n : 0.0;
+    const double overall = (acc_mean + comp_mean) / 2.0;
+    std::printf("DTU protocol: density %s, max_dist %s, %s\n", fmt_f32(opt.dtu_density).c_str(),
+                fmt_f32(opt.dtu_max_dist).c_str(),
+                opt.dtu_no_thin ? "not thinned" : ("seed " + std::to_string(opt.dtu_seed)).c_str());
+    std::printf("input points: %lld\nthinned points: %lld\nin mask points: %lld\n", (long long)n_in, (long long)n_data,
+                (long long)n_inside);
+    std::printf("gt points: %lld\ngt above plane points: %lld\n", (long long)n_gt, (long long)n_above);
+    std::printf("accuracy selected: %lld\ncompleteness selected: %lld\n", (long long)acc_n, (long long)comp_n);
+    std::printf("accuracy mean: %s\naccuracy median: %s\ncompleteness mean: %s\ncompleteness median: %s\noverall: %s\n",
+                fmt_g(acc_mean).c_str(), fmt_g(acc_med).c_str(), fmt_g(comp_mean).c_str(), fmt_g(comp_med).c_str(),
+                fmt_g(overall).c_str());
+    json += std::string("\"dtu\": {\"definition\": \"modelled on the DTU evaluation (radius thinning, observability "
+                        "mask, table plane, mean and median of the distances below max_dist) with this project's own "
+                        "contract: a seeded Philox order instead of randperm, doubles for the mask index, <= the float "
+                        "below max_dist, no chunks; parity with the MATLAB code is not pinned\", \"density\": ") +
+            fmt_g((double)opt.dtu_density) + ", \"max_dist\": " + fmt_g((double)opt.dtu_max_dist) + ", \"seed\": " +
+            std::to_string(opt.dtu_seed) + ", \"thinned\": " + (opt.dtu_no_thin ? "false" : "true") +
+            ", \"input_points\": " + std::to_string(n_in) + ", \"thinned_points\": " + std::to_string(n_data) +
+            ", \"in_mask_points\": " + std::to_string(n_inside) + ", \"gt_points\": " + std::to_string(n_gt) +
+            ", \"gt_above_plane_points\": " + std::to_string(n_above) + ", \"accuracy_selected\": " +
+            std::to_string(acc_n) + ", \"completeness_selected\": " + std::to_string(comp_n) + ", \"accuracy_mean\": " +
+            fmt_g(acc_mean) + ", \"accuracy_median\": " + fmt_g(acc_med) + ", \"completeness_mean\": " +
+            fmt_g(comp_mean) + ", \"completeness_median\": " + fmt_g(comp_med) + ", \"overall\": " + fmt_g(overall) +
+            ", \"thin_rounds\": " + std::to_string(rounds) + ", \"thin_sort_ms\": " + fmt_g(sort_ms) +
+            ", \"thin_rounds_ms\": " + fmt_g(rounds_ms) + ", \"build_ms\": " + fmt_g(build_ms) + ", \"query_ms\": " +
+            fmt_g(query_ms) + ", \"mask_ms\": " + fmt_g(mask_ms) + ", \"half_space_ms\": " + fmt_g(plane_ms) +
+            ", \"stats_ms\": " + fmt_g(stats_ms) + "}";
+    return 0;
+}
+
 // ---- depth mode ---------------------------------------------------------------------------------
 
 struct DepthStats {
@@ -1118,6 +1296,7 @@ int main(int argc, char **argv) {
         if (a == "--no_refine") { opt.no_refine = true; continue; }
         if (a == "--no_scale") { opt.no_scale = true; continue; }
         if (a == "--tat_dump") { opt.tat_dump = true; continue; }
+        if (a == "--dtu_no_thin") { opt.dtu_no_thin = opt.dtu_option_given = true; continue; }
         if (i + 1 >= argc) return bad("missing value for " + a);
         const std::string v = argv[++i];
         if (a == "--cloud") opt.cloud = v;
@@ -1139,6 +1318,28 @@ int main(int argc, char **argv) {
         else if (a == "--tat_trans") opt.tat_trans = v;
         else if (a == "--init_trans") opt.init_trans = v;
         else if (a == "--aligned_cloud_out") opt.aligned_out = v;
+        else if (a == "--dtu_gt") opt.dtu_gt = v;
+        else if (a == "--dtu_mask") { opt.dtu_mask = v; opt.dtu_option_given = true; }
+        else if (a == "--dtu_plane") { opt.dtu_plane = v; opt.dtu_option_given = true; }
+        else if (a == "--thinned_cloud_out") { opt.thinned_out = v; opt.dtu_option_given = true; }
+        else if (a == "--dtu_density") {
+            // the bounds of include/apd_eval.h's radius: its fp32 square must be a normal number
+            if (!parse_float(v, opt.dtu_density) || !(opt.dtu_density >= 1.1e-19f) || !(opt.dtu_density <= 1.8e19f))
+                return bad("bad --dtu_density " + v);
+            opt.dtu_option_given = true;
+        } else if (a == "--dtu_max_dist") {
+            if (!parse_float(v, opt.dtu_max_dist) || !(opt.dtu_max_dist > 0.0f) || !std::isfinite(opt.dtu_max_dist))
+                return bad("bad --dtu_max_dist " + v);
+            opt.dtu_option_given = true;
+        } else if (a == "--dtu_seed") {
+            char *end = nullptr;
+            errno = 0;
+            const unsigned long long s = std::strtoull(v.c_str(), &end, 10);
+            if (v.empty() || v[0] == '-' || !end || *end != '\0' || errno != 0 || s > 0xFFFFFFFFull)
+                return bad("bad --dtu_seed " + v + " (0..4294967295)");
+            opt.dtu_seed = (uint32_t)s;
+            opt.dtu_option_given = true;
+        }
         else if (a == "--tau") {
             if (!parse_float(v, opt.tau) || !(opt.tau > 0.0f) || !std::isfinite(opt.tau)) return bad("bad --tau " + v);
             opt.tau_given = true;
@@ -1192,7 +1393,8 @@ int main(int argc, char **argv) {
     }
     const bool tat_mode = !opt.tat_gt.empty() || opt.tat_dump;
     const bool scanner_mode = !opt.gt_mlp.empty();
-    const bool cloud_mode = !scanner_mode && !tat_mode && (!opt.cloud.empty() || !opt.gt.empty());
+    const bool dtu_mode = !opt.dtu_gt.empty();
+    const bool cloud_mode = !scanner_mode && !tat_mode && !dtu_mode && (!opt.cloud.empty() || !opt.gt.empty());
     const bool depth_mode = !opt.dense.empty() || !opt.against.empty() || !opt.gt_depth.empty() || !opt.gt_cloud.empty();
     const bool render_mode = !opt.render_gt.empty();
     if (scanner_mode) {
@@ -1225,7 +1427,17 @@ int main(int argc, char **argv) {
         return bad("--tat_crop / --tat_trans / --init_trans / --tau / --no_refine / --refine_stages / --no_scale / "
                    "--aligned_cloud_out without --tat_gt");
     }
-    if (!cloud_mode && !depth_mode && !render_mode && !scanner_mode && !tat_mode) return bad("nothing to do");
+    if (dtu_mode) {
+        if (scanner_mode || tat_mode || depth_mode || render_mode || !opt.gt.empty() || opt.visible_views > 0 ||
+            !opt.scan.empty() || opt.voxel_given || opt.max_dist >= 0.0f)
+            return bad("--dtu_gt excludes the other modes and their options");
+        if (opt.cloud.empty() || opt.dtu_mask.empty() || opt.dtu_plane.empty())
+            return bad("DTU mode needs --cloud, --dtu_gt, --dtu_mask and --dtu_plane");
+    } else if (opt.dtu_option_given) {
+        return bad("--dtu_mask / --dtu_plane / --dtu_density / --dtu_max_dist / --dtu_seed / --dtu_no_thin / "
+                   "--thinned_cloud_out without --dtu_gt");
+    }
+    if (!cloud_mode && !depth_mode && !render_mode && !scanner_mode && !tat_mode && !dtu_mode) return bad("nothing to do");
     if (cloud_mode && (opt.cloud.empty() || opt.gt.empty())) return bad("cloud mode needs --cloud and --gt");
     if (depth_mode && (opt.dense.empty() ||
                        (int)!opt.against.empty() + (int)!opt.gt_depth.empty() + (int)!opt.gt_cloud.empty() != 1))
@@ -1276,6 +1488,10 @@ int main(int argc, char **argv) {
         if (opt.tat_dump) return run_tat_dump(tin, !opt.tat_crop.empty());
         if (!read_ply_xyz(opt.cloud, tin.rec, err) || !read_ply_xyz(opt.tat_gt, tin.gt, err)) return unreadable();
     }
+    DtuInputs uin;
+    if (dtu_mode && (!read_dtu_side_files(opt, uin, err) || !read_ply_xyz(opt.cloud, uin.rec, err) ||
+                     !read_ply_xyz(opt.dtu_gt, uin.gt, err)))
+        return unreadable();
     if (scanner_mode) {
         std::vector<MlpMesh> meshes;
         if (!read_ply_xyz(opt.cloud, sin.rec.xyz, err) || !read_mlp(opt.gt_mlp, meshes, err)) return unreadable();
@@ -1321,6 +1537,12 @@ int main(int argc, char **argv) {
         const int st = run_tat(opt, tin, json);
         status = std::max(status, st);
         if (st != 0) json += "\"tat\": null";
+    }
+    if (dtu_mode) {
+        sep();
+        const int st = run_dtu(opt, uin, json);
+        status = std::max(status, st);
+        if (st != 0) json += "\"dtu\": null";
     }
     if (render_mode) {
         sep();

@@ -5,6 +5,7 @@
 #include <mutex>
 
 #include <sys/stat.h>
+#include <zlib.h>
 
 #include <algorithm>
 #include <cctype>
@@ -673,6 +674,260 @@ bool read_matrix4(const std::string &path, double M[16], std::string &err) {
     }
     if (k < 16) return fail(std::to_string(k) + " numbers, 16 (a 4x4 matrix) expected");
     if (M[12] != 0.0 || M[13] != 0.0 || M[14] != 0.0 || M[15] != 1.0) return fail("the last row is not 0 0 0 1");
+    return true;
+}
+
+// ----------------------------------------------------------------------------------------------
+// Level-5 MAT-files
+// ----------------------------------------------------------------------------------------------
+namespace {
+
+enum : uint32_t { kMiInt8 = 1, kMiUint8 = 2, kMiInt16 = 3, kMiUint16 = 4, kMiInt32 = 5, kMiUint32 = 6, kMiSingle = 7,
+                  kMiDouble = 9, kMiInt64 = 12, kMiUint64 = 13, kMiMatrix = 14, kMiCompressed = 15, kMiUtf8 = 16 };
+
+uint32_t mat_u32(const uint8_t *p) { return (uint32_t)p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24; }
+
+// bytes per value of a numeric storage type, 0 for any other
+size_t mat_type_size(uint32_t mi) {
+    switch (mi) {
+    case kMiInt8: case kMiUint8: return 1;
+    case kMiInt16: case kMiUint16: return 2;
+    case kMiInt32: case kMiUint32: case kMiSingle: return 4;
+    case kMiDouble: case kMiInt64: case kMiUint64: return 8;
+    default: return 0;
+    }
+}
+
+double mat_value(uint32_t mi, const uint8_t *p) {
+    switch (mi) {
+    case kMiInt8: return (double)(int8_t)p[0];
+    case kMiUint8: return (double)p[0];
+    case kMiInt16: { int16_t v; std::memcpy(&v, p, 2); return (double)v; }
+    case kMiUint16: { uint16_t v; std::memcpy(&v, p, 2); return (double)v; }
+    case kMiInt32: { int32_t v; std::memcpy(&v, p, 4); return (double)v; }
+    case kMiUint32: { uint32_t v; std::memcpy(&v, p, 4); return (double)v; }
+    case kMiSingle: { float v; std::memcpy(&v, p, 4); return (double)v; }
+    case kMiDouble: { double v; std::memcpy(&v, p, 8); return v; }
+    case kMiInt64: { int64_t v; std::memcpy(&v, p, 8); return (double)v; }
+    default: { uint64_t v; std::memcpy(&v, p, 8); return (double)v; }
+    }
+}
+
+// One sub-element at offset `off` of a parent whose tag declares `declared` bytes, of which `avail`
+// are at hand. data / nbytes: its payload; next: the offset behind its padding.
+struct MatSub {
+    uint32_t type = 0, nbytes = 0;
+    size_t data = 0, next = 0;
+};
+bool mat_sub(const uint8_t *b, size_t avail, size_t declared, size_t off, MatSub &s, std::string &what) {
+    if (off + 8 > declared) { what = "a sub-element tag overruns its matrix"; return false; }
+    if (off + 8 > avail) { what = "truncated inside a matrix"; return false; }
+    const uint32_t w0 = mat_u32(b + off);
+    if (w0 >> 16) {  // the small form: type in the low half, 1 to 4 bytes of payload inside the tag
+        s.type = w0 & 0xFFFFu;
+        s.nbytes = w0 >> 16;
+        if (s.nbytes > 4) { what = "a small element of more than 4 bytes"; return false; }
+        s.data = off + 4;
+        s.next = off + 8;
+        return true;
+    }
+    s.type = w0;
+    s.nbytes = mat_u32(b + off + 4);
+    s.data = off + 8;
+    if ((uint64_t)s.nbytes > (uint64_t)(declared - s.data)) { what = "a byte count overruns its matrix"; return false; }
+    if (s.data + s.nbytes > avail) { what = "truncated inside a matrix"; return false; }
+    s.next = s.data + (((size_t)s.nbytes + 7) & ~(size_t)7);
+    return true;
+}
+
+struct MatHead {
+    std::string name;
+    uint32_t cls = 0;
+    bool complex = false, logical = false;
+    std::vector<int64_t> dims;
+    size_t data_off = 0;  // offset of the real part's tag
+};
+// flags, dimensions and name of a matrix body; false with `what` set if malformed
+bool mat_head(const uint8_t *b, size_t avail, size_t declared, MatHead &h, std::string &what) {
+    MatSub s;
+    if (!mat_sub(b, avail, declared, 0, s, what)) return false;
+    if (s.type != kMiUint32 || s.nbytes != 8) { what = "no array flags at the start of a matrix"; return false; }
+    const uint32_t flags = mat_u32(b + s.data);
+    h.cls = flags & 0xFFu;
+    h.complex = (flags & 0x0800u) != 0;
+    h.logical = (flags & 0x0200u) != 0;
+    if (!mat_sub(b, avail, declared, s.next, s, what)) return false;
+    if (s.type != kMiInt32 || s.nbytes % 4 != 0 || s.nbytes == 0 || s.nbytes > 4 * 32) {
+        what = "a matrix without a dimensions array of 1 to 32 int32";
+        return false;
+    }
+    h.dims.clear();
+    for (uint32_t k = 0; k < s.nbytes / 4; ++k) {
+        const int32_t d = (int32_t)mat_u32(b + s.data + 4 * k);
+        if (d < 0) { what = "a negative dimension"; return false; }
+        h.dims.push_back(d);
+    }
+    if (!mat_sub(b, avail, declared, s.next, s, what)) return false;
+    if ((s.type != kMiInt8 && s.type != kMiUint8 && s.type != kMiUtf8) || s.nbytes > 255) {
+        what = "a matrix name that is not 0 to 255 bytes of text";
+        return false;
+    }
+    h.name.assign((const char *)b + s.data, s.nbytes);
+    h.data_off = s.next;
+    return true;
+}
+
+const char *mat_class_name(uint32_t cls) {
+    switch (cls) {
+    case 1: return "a cell array";
+    case 2: return "a struct";
+    case 3: return "an object";
+    case 4: return "a char array";
+    case 5: return "sparse";
+    default: return "of an unsupported class";
+    }
+}
+
+// the values of a wanted matrix whose whole body is at hand
+bool mat_take(const uint8_t *b, size_t len, const MatHead &h, bool as_mask, MatArray &a, std::string &what) {
+    if (h.cls < 6 || h.cls > 15) { what = std::string("is ") + mat_class_name(h.cls); return false; }
+    if (h.complex) { what = "is complex"; return false; }
+    if (h.dims.size() > 3) { what = "has more than 3 dimensions"; return false; }
+    if (as_mask && !h.logical && h.cls != 9) { what = "is neither logical nor uint8"; return false; }
+    uint64_t count = 1;
+    for (int64_t d : h.dims) {
+        count *= (uint64_t)d;  // each factor is below 2^31 and the product is checked every step: no overflow
+        if (count > kMatMaxElems) { what = "has more than 2^31 elements"; return false; }
+    }
+    MatSub s;
+    if (!mat_sub(b, len, len, h.data_off, s, what)) return false;
+    const size_t size = mat_type_size(s.type);
+    if (size == 0) { what = "stores its values in an unsupported type"; return false; }
+    if ((uint64_t)s.nbytes != count * size) { what = "holds a byte count that does not match its dimensions"; return false; }
+    a.name = h.name;
+    a.dims = h.dims;
+    a.logical = h.logical;
+    const uint8_t *p = b + s.data;
+    if (as_mask) {
+        a.bytes.resize((size_t)count);
+        for (size_t i = 0; i < (size_t)count; ++i) a.bytes[i] = mat_value(s.type, p + i * size) != 0.0 ? 1 : 0;
+    } else {
+        a.values.resize((size_t)count);
+        for (size_t i = 0; i < (size_t)count; ++i) a.values[i] = mat_value(s.type, p + i * size);
+    }
+    return true;
+}
+
+// zlib inflation in steps; the output at most doubles per step (never less than 64 KiB at a time)
+struct MatInflater {
+    z_stream zs{};
+    bool init = false, done = false;
+    std::vector<uint8_t> out;
+    ~MatInflater() {
+        if (init) inflateEnd(&zs);
+    }
+    bool begin(const uint8_t *p, size_t n) {
+        zs.next_in = const_cast<Bytef *>(p);
+        zs.avail_in = (uInt)n;  // n <= kMatMaxFile
+        init = inflateInit(&zs) == Z_OK;
+        return init;
+    }
+    // inflate until the output holds `upto` bytes or the stream ends; false: corrupt or cut short
+    bool fill(size_t upto) {
+        while (!done && out.size() < upto) {
+            const size_t have = out.size();
+            const size_t chunk = std::min(upto - have, std::max<size_t>((size_t)1 << 16, have));
+            out.resize(have + chunk);
+            zs.next_out = out.data() + have;
+            zs.avail_out = (uInt)chunk;
+            const int r = inflate(&zs, Z_NO_FLUSH);
+            const size_t got = chunk - zs.avail_out;
+            out.resize(have + got);
+            if (r == Z_STREAM_END) done = true;
+            else if (r != Z_OK || got == 0) return false;
+        }
+        return true;
+    }
+};
+
+}  // namespace
+
+bool read_mat5(const std::string &path, const std::vector<MatWanted> &wanted, std::vector<MatArray> &out,
+               std::string &err) {
+    std::string file;
+    out.clear();
+    if (!read_text_bounded(path, (size_t)kMatMaxFile, "2 GiB", file, err)) return false;
+    auto fail = [&](const std::string &what) { err = path + ": " + what; out.clear(); return false; };
+    const uint8_t *f = (const uint8_t *)file.data();
+    const size_t size = file.size();
+    if (size >= 10 && file.compare(0, 10, "MATLAB 7.3") == 0)
+        return fail("a MATLAB 7.3 (HDF5) file; re-save it with -v7");
+    if (size < 128) return fail("shorter than the 128-byte header of a Level-5 MAT-file");
+    if (f[126] == 'M' && f[127] == 'I') return fail("a big-endian MAT-file");
+    if (f[126] != 'I' || f[127] != 'M') return fail("no MAT-file endian indicator");
+    if (f[124] != 0x00 || f[125] != 0x01) return fail("not version 0x0100 of the MAT-file format");
+    std::vector<bool> found(wanted.size(), false);
+    out.resize(wanted.size());
+    auto want = [&](const std::string &name) {
+        for (size_t k = 0; k < wanted.size(); ++k)
+            if (wanted[k].name == name) return (int)k;
+        return -1;
+    };
+    // a matrix body with `avail` of its `declared` bytes at hand: <0 malformed, 0 not wanted, 1 wanted
+    auto head = [&](const uint8_t *b, size_t avail, size_t declared, MatHead &h, int &slot) {
+        std::string what;
+        slot = -1;
+        if (declared == 0) return 0;  // an empty matrix has no name
+        if (!mat_head(b, avail, declared, h, what)) { fail(what); return -1; }
+        slot = want(h.name);
+        if (slot < 0) return 0;
+        if (found[(size_t)slot]) { fail("variable '" + h.name + "' occurs twice"); return -1; }
+        return 1;
+    };
+    auto take = [&](const uint8_t *b, size_t len, const MatHead &h, int slot) {
+        std::string what;
+        if (!mat_take(b, len, h, wanted[(size_t)slot].as_mask, out[(size_t)slot], what))
+            return fail("variable '" + h.name + "' " + what);
+        found[(size_t)slot] = true;
+        return true;
+    };
+    size_t pos = 128;
+    while (pos < size) {
+        if (size - pos < 8) return fail("truncated inside an element tag");
+        const uint32_t type = mat_u32(f + pos), nbytes = mat_u32(f + pos + 4);
+        if ((type >> 16) != 0) return fail("a small element at the top level");
+        if ((uint64_t)nbytes > (uint64_t)(size - pos - 8)) return fail("an element's byte count overruns the file");
+        const uint8_t *body = f + pos + 8;
+        MatHead h;
+        int slot;
+        if (type == kMiMatrix) {
+            const int r = head(body, nbytes, nbytes, h, slot);
+            if (r < 0 || (r > 0 && !take(body, nbytes, h, slot))) return false;
+        } else if (type == kMiCompressed) {
+            MatInflater z;
+            if (!z.begin(body, nbytes)) return fail("zlib could not start");
+            if (!z.fill(8) || z.out.size() < 8) return fail("a compressed element that does not inflate to a tag");
+            const uint32_t itype = mat_u32(z.out.data()), ibytes = mat_u32(z.out.data() + 4);
+            if (itype == kMiMatrix) {
+                const uint64_t total = 8 + (uint64_t)ibytes;
+                if (total > kMatMaxInflated) return fail("a compressed element declares more than the 2 GiB inflation cap");
+                if (!z.fill((size_t)std::min<uint64_t>(total, (uint64_t)1 << 16)))
+                    return fail("a compressed element is corrupt or cut short");
+                const int r = head(z.out.data() + 8, z.out.size() - 8, ibytes, h, slot);
+                if (r < 0) return false;
+                if (r > 0) {
+                    // one byte beyond the declared size shows a stream that goes on
+                    if (!z.fill((size_t)total + 1)) return fail("a compressed element is corrupt or cut short");
+                    if (z.out.size() > total) return fail("a compressed element inflates past its declared size");
+                    if (z.out.size() < total) return fail("a compressed element inflates to less than its declared size");
+                    if (!take(z.out.data() + 8, ibytes, h, slot)) return false;
+                }
+            }
+        }
+        pos += 8 + (size_t)nbytes;
+    }
+    for (size_t k = 0; k < wanted.size(); ++k)
+        if (!found[k]) return fail("variable '" + wanted[k].name + "' is missing");
     return true;
 }
 

@@ -145,6 +145,37 @@ bool read_tat_crop(const std::string &path, TatCrop &crop, std::string &err);
 // inf, nan, a leading '+' or '.') or lies outside the double range, a last row other than 0 0 0 1.
 bool read_matrix4(const std::string &path, double M[16], std::string &err);
 
+// ---- DTU ground-truth side files (apd_eval --dtu_gt): Level-5 MAT-files ------------------------------
+struct MatWanted {
+    std::string name;
+    bool as_mask = false;  // a logical or uint8 array, delivered as bytes (1 where non-zero)
+};
+struct MatArray {
+    std::string name;
+    std::vector<int64_t> dims;  // 1 to 3, each >= 0, as in the file
+    bool logical = false;
+    std::vector<double> values;  // column-major, every stored type converted to double (not as_mask)
+    std::vector<uint8_t> bytes;  // as_mask
+};
+constexpr uint64_t kMatMaxFile = (uint64_t)1 << 31;                    // bytes of a file
+constexpr uint64_t kMatMaxInflated = ((uint64_t)1 << 31) + (1 << 16);  // bytes of one inflated element
+constexpr uint64_t kMatMaxElems = (uint64_t)1 << 31;                   // elements of one array
+// The wanted variables of a little-endian Level-5 MAT-file (128-byte header, version 0x0100, endian
+// indicator "IM"), in the order of `wanted`. Top-level elements are miMATRIX, or miCOMPRESSED (zlib)
+// holding one miMATRIX; per matrix: array flags, 1 to 3 dimensions, name, real part, with the small
+// tag form and the 8-byte padding. Classes double, single and int8..uint64 (with the logical flag);
+// stored data type any of miINT8..miUINT64, miSINGLE, miDOUBLE (MATLAB narrows integral doubles).
+// Variables not asked for are skipped whatever their class, a compressed one after its first 64 KiB.
+// Rejected with a message naming the file (and the variable): a wanted name that is missing, occurs
+// twice, is complex, sparse, a cell, struct, object or char array or has more than 3 dimensions; a
+// "MATLAB 7.3" (HDF5) file, with the advice to re-save with -v7; a big-endian file ("MI"); any tag or
+// byte count that overruns its parent or the file; more than kMatMaxElems elements; a file above
+// kMatMaxFile; a compressed element that declares or inflates to more than kMatMaxInflated or past its
+// own declared size. Nothing is allocated before the bytes that justify it are known to be in the
+// file: inflation is incremental and its output at most doubles per step.
+bool read_mat5(const std::string &path, const std::vector<MatWanted> &wanted, std::vector<MatArray> &out,
+               std::string &err);
+
 // ---- COLMAP sparse models (apd_prepare; the reference's tools/colmap2mvsnet.py) ---------------------
 struct ColmapCamera {
     uint32_t id = 0;

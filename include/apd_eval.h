@@ -10,7 +10,9 @@
  * A scanner free-space test and voxel-averaged scores, modelled on the ETH3D protocol with a contract
  * of their own, are declared after them (parity with the ETH3D tool is not pinned). A crop volume,
  * the nearest neighbour with its index, a similarity transform and point-to-point ICP registration, the
- * steps of the Tanks and Temples protocol, close the header, each with a host twin.
+ * steps of the Tanks and Temples protocol, follow, each with a host twin. Exact radius thinning, an
+ * observability mask, a half-space test and masked mean / median statistics, the steps of the DTU
+ * protocol, close the header, each with a host twin.
  *
  * Distance contract (bit for bit, all arithmetic fp32 and nothing contracted):
  *   - a target with a non-finite coordinate never matches; a query with one gives +inf
@@ -283,6 +285,93 @@ int32_t apd_eval_register_sums_host(int64_t nt, const float *target, int64_t n, 
    Any pointer may be NULL. */
 int32_t apd_eval_get_register_timing(apd_eval_ctx *ctx, double *eval_ms, double *fold_ms, double *solve_ms,
                                      int32_t *evaluations, double *crop_ms, double *transform_ms);
+
+/* ---- radius thinning, observability mask, half-space, masked statistics ------------------------------
+ * The steps the DTU evaluation protocol adds around the distances: the reconstruction is thinned to a
+ * minimum point spacing, accuracy counts only the points inside the scan's observability mask (a 3-D
+ * byte volume), completeness only the ground-truth points above the table plane, and the scores are
+ * the mean and the median of the distances below a limit. The contract is this project's own (bit for
+ * bit between the device calls and their host twins, and the same from run to run); parity with the
+ * DTU MATLAB code is not pinned.
+ *
+ * Radius thinning (the greedy maximal independent set of the radius graph, MATLAB's reducePts_haa with
+ * a stated order). rank is n uint32 values, NULL meaning all equal; the priority key of point i is
+ * ((uint64)rank[i] << 32) | i, lower goes first; ranks need not be distinct.
+ *   - a point with a non-finite coordinate is never kept and suppresses nothing
+ *   - i and j are close iff d2 <= r2, d2 = (dx*dx + dy*dy) + dz*dz the distance contract's (fp32,
+ *     nothing contracted, dx = x_i - x_j), r2 = radius*radius (one fp32 product). Equality counts.
+ *   - visiting the finite points in ascending key, a point is kept iff no point kept before it is
+ *     close to it.
+ * radius is valid iff r2 is a finite normal fp32 number (about 1.1e-19 <= radius <= 1.8e19): below
+ * that the fp32 products underflow and `close` no longer bounds the coordinate differences.
+ * Candidates are found in a grid of cell 2*radius, cell index floor((double)x / (2.0*radius)) per axis;
+ * every decision is made by the d2 <= r2 test alone, so the grid does not enter the result. The
+ * device runs the two final rules "removed once a close lower-key point is kept" and "kept once every
+ * close lower-key point is removed" over a shrinking worklist until no point is undecided; that
+ * fixed point is unique and equals the loop above.
+ *
+ * Observability mask. mask is dims[0]*dims[1]*dims[2] bytes in column-major order (MATLAB's). In
+ * double: v_k = round(((double)x_k - origin[k]) / res + 1.0), C round (half away from zero).
+ *   inside[i] = 1 iff the three coordinates are finite, 1 <= v_k <= dims[k] for all k and
+ *   mask[(v_0 - 1) + dims[0]*((v_1 - 1) + dims[1]*(v_2 - 1))] != 0; else 0.
+ *
+ * Half-space. above[i] = 1 iff ((P[0]*x + P[1]*y) + P[2]*z) + P[3] > 0 in double, the coordinates
+ * converted to double, nothing contracted; a NaN compares false. Else 0.
+ *
+ * Masked statistics of n fp32 distances. Point i is selected iff (flag == NULL or flag[i] != 0),
+ * dist[i] <= limit and dist[i] < +inf (a NaN is never selected).
+ *   count  = the number of selected points, exact
+ *   sum    = the double sum of the selected distances, +0.0 standing for the others, in the summation
+ *            order of the registration contract: blocks of APD_EVAL_REG_BLOCK indices, the balanced
+ *            binary tree inside a block, the blocks left to right from block 0's sum (no block: +0.0)
+ *   median = from the selected distances s in ascending order (the order of their sign-magnitude bits,
+ *            so -0 < +0): odd count m: s[(m - 1)/2]; even: ((double)s[m/2 - 1] + (double)s[m/2]) / 2;
+ *            m = 0: 0.
+ */
+
+/* keep_idx (room for n entries): the ascending indices of the kept points, *n_keep their number; both,
+   xyz and rank may be host or device pointers.
+   APD_EINVAL: n out of range, xyz, keep_idx NULL with n > 0, n_keep NULL, a radius that is not valid
+   (above), an axis whose occupied cells span more than 2^21 (the packed key has 63 bits). */
+int32_t apd_eval_radius_thin(apd_eval_ctx *ctx, int64_t n, const float *xyz, float radius, const uint32_t *rank,
+                             int32_t *keep_idx, int64_t *n_keep);
+/* Host twin: the loop itself on one thread; no context, no device; every pointer is host memory. */
+int32_t apd_eval_radius_thin_host(int64_t n, const float *xyz, float radius, const uint32_t *rank, int32_t *keep_idx,
+                                  int64_t *n_keep);
+/* Device-event times of the last apd_eval_radius_thin call (sort_ms: bounds, keys, sort, gather and
+   the neighbour runs; rounds_ms: the rounds and the final compaction) and its number of rounds. */
+int32_t apd_eval_get_thin_timing(apd_eval_ctx *ctx, double *sort_ms, double *rounds_ms, int32_t *rounds);
+
+/* rank[i] = word 0 of Philox4x32-10 with counter (i, 0, 0, 0) and key (seed, 0), the generator of the
+   depth engine. Host only. APD_EINVAL: n out of range, rank NULL with n > 0. */
+int32_t apd_eval_dtu_ranks(int64_t n, uint32_t seed, uint32_t *rank);
+
+/* inside: n bytes. mask is uploaded once and kept in the context while the same pointer and dims are
+   given (a caller that rewrites the array in place passes it through another call first, or destroys
+   the context). xyz, mask and inside may be host or device pointers; dims and origin are host memory.
+   APD_EINVAL: n out of range, a NULL pointer (xyz and inside only with n > 0), a dim < 1, a product
+   of dims above 2^31, res not positive and finite, a non-finite origin. */
+int32_t apd_eval_obs_mask(apd_eval_ctx *ctx, int64_t n, const float *xyz, const int32_t dims[3],
+                          const double origin[3], double res, const uint8_t *mask, uint8_t *inside);
+int32_t apd_eval_obs_mask_host(int64_t n, const float *xyz, const int32_t dims[3], const double origin[3], double res,
+                               const uint8_t *mask, uint8_t *inside);
+
+/* above: n bytes; xyz and above may be host or device pointers, P is host memory.
+   APD_EINVAL: n out of range, P NULL, xyz or above NULL with n > 0. */
+int32_t apd_eval_half_space(apd_eval_ctx *ctx, int64_t n, const float *xyz, const double P[4], uint8_t *above);
+int32_t apd_eval_half_space_host(int64_t n, const float *xyz, const double P[4], uint8_t *above);
+
+/* dist (n floats) and flag (n bytes, may be NULL) may be host or device pointers; count, sum and
+   median are host memory and may each be NULL.
+   APD_EINVAL: n out of range, dist NULL with n > 0, a NaN limit. */
+int32_t apd_eval_masked_stats(apd_eval_ctx *ctx, int64_t n, const float *dist, const uint8_t *flag, float limit,
+                              int64_t *count, double *sum, double *median);
+int32_t apd_eval_masked_stats_host(int64_t n, const float *dist, const uint8_t *flag, float limit, int64_t *count,
+                                   double *sum, double *median);
+
+/* Device-event times of the last obs_mask / half_space / masked_stats call (kernels and sort, without
+   the mask upload). Any pointer may be NULL. */
+int32_t apd_eval_get_dtu_timing(apd_eval_ctx *ctx, double *mask_ms, double *half_space_ms, double *stats_ms);
 
 #ifdef __cplusplus
 }
