@@ -1741,6 +1741,31 @@ int oracle_run_patchmatch(const apd_problem *pb, const apd_outputs *out, int nth
     return APD_OK;
 }
 
+/* RunPatchMatch stopped part-way, for the staged comparison with the HIP engine's stages
+   (tests/test_gpu_staged_parity.py): run_prepare, the first n_iterations loop bodies, run_finish only
+   if do_finish; the state at that point goes to out. Mid-run planes are in the sweep's form
+   (reference-frame normal, distance to the origin), as before GetDepthandNormal (APD.cu:1694-1709).
+   n_iterations = max_iterations with do_finish = 1 is oracle_run_patchmatch. */
+int oracle_run_staged(const apd_problem *pb, const apd_outputs *out, int n_iterations, int do_finish, int nthreads) {
+#ifdef _OPENMP
+    if (nthreads > 0) omp_set_num_threads(nthreads);
+#else
+    (void)nthreads;
+#endif
+    octx *o = (octx *)malloc(sizeof(octx));
+    if (!o) return APD_ENOMEM;
+    int st = ctx_init(o, pb);
+    if (st != APD_OK) { ctx_free(o); free(o); return st; }
+    o->curve = out ? out->reliable_curve : NULL;
+    run_prepare(o);
+    for (int it = 0; it < n_iterations; ++it) run_iteration(o, it);
+    if (do_finish) run_finish(o);
+    if (out) ctx_output(o, out);
+    ctx_free(o);
+    free(o);
+    return APD_OK;
+}
+
 /* Bounded CPU-baseline sample: prepare, then `iters` sweep iterations over only the first
    `max_rows` rows' worth of pixels is not meaningful for a checkerboard, so the baseline instead runs
    the real sweep on the full image and reports per-iteration seconds in times[1]/iters. */
@@ -1837,9 +1862,23 @@ float oracle_ncc_new(const apd_problem *pb, int px, int py, int src, const float
      stage 3  FindNearestStrongPoint + GenAnchors (APD.cu:1857-2082) + NeigbourUpdate
               (APD.cu:2084-2100): planes (in, as during the sweep), weak (in/out), conf (in) ->
               anchors (out, weak_count x 9 x (x, y), row-major WEAK order of the input), reliable (out).
+     Stages of the Strong half and the fit (tests/test_oracle_kat_strong.py), through
+     oracle_kat_stage_ex only; planes are in the sweep's form (reference-frame normal, distance to the
+     origin) unless noted, and sel, costs, vw (view-major, N x H*W) are in/out, fit (4 floats per
+     pixel) is out:
+     stage 4  RandomInitialization + ComputeMultiViewInitialCostandSelectedViews (APD.cu:919-948,
+              723-774): planes (in as pb->init_planes has them: world normal, depth; unused in
+              FIRST_INIT) -> planes, costs, sel;
+     stage 5  one colour (0 black, 1 red) of CheckerboardPropagationStrong +
+              PlaneHypothesisRefinementStrong at `iter` (APD.cu:1098-1440, 950-1006) over the non-WEAK
+              pixels: planes, costs, sel (in/out), vw (out);
+     stage 6  RANSACToGetFitPlane at `iter` (APD.cu:2486-2598) with caller-given anchors (in,
+              weak_count x 9 x (x, y), row-major WEAK order): planes, weak (in) -> fit;
+     stage 7  LocalRefine (APD.cu:2346-2432): planes (world normal, depth; in/out), sel, vw (in).
    Returns APD_OK or a negative status. */
-int oracle_kat_stage(const apd_problem *pb, int stage, const uint32_t *sel, const float *costs, float *planes,
-                     uint8_t *weak, uint8_t *conf, int16_t *nearest, int16_t *anchors, uint8_t *reliable) {
+int oracle_kat_stage_ex(const apd_problem *pb, int stage, int iter, int colour, uint32_t *sel, float *costs,
+                        float *planes, uint8_t *weak, uint8_t *conf, int16_t *nearest, int16_t *anchors,
+                        uint8_t *reliable, uint8_t *vw, float *fit) {
     octx *o = (octx *)malloc(sizeof(octx));
     if (!o) return APD_ENOMEM;
     int st = kat_ctx(o, pb);
@@ -1850,6 +1889,21 @@ int oracle_kat_stage(const apd_problem *pb, int stage, const uint32_t *sel, cons
     if (sel) memcpy(o->sel, sel, HW * sizeof(uint32_t));
     if (weak) memcpy(o->weak, weak, HW);
     if (conf) memcpy(o->conf, conf, HW);
+    if (stage >= 4) {
+        if (vw) memcpy(o->vw, vw, HW * (size_t)o->N);
+        if (weak) { /* the WEAK index follows the caller's states */
+            int32_t wc = 0;
+            for (size_t i = 0; i < HW; ++i) o->amap[i] = (o->weak[i] == WEAK) ? wc++ : -1;
+            if (wc > o->weak_count) {
+                free(o->anchors);
+                o->anchors = (int16_t *)calloc((size_t)wc * ANCHOR_NUM * 2, sizeof(int16_t));
+                if (!o->anchors) { o->weak_count = 0; ctx_free(o); free(o); return APD_ENOMEM; }
+            }
+            o->weak_count = wc;
+        }
+        if (stage == 6 && anchors && o->weak_count > 0)
+            memcpy(o->anchors, anchors, (size_t)o->weak_count * ANCHOR_NUM * 2 * sizeof(int16_t));
+    }
     switch (stage) {
     case 0:
         FOR_COLOUR(o, 0, if (RD(o, weak, py * o->W + px) != WEAK) k_filter(o, px, py));
@@ -1871,8 +1925,31 @@ int oracle_kat_stage(const apd_problem *pb, int stage, const uint32_t *sel, cons
         });
         break;
     }
+    case 4:
+        FOR_ALL(o, k_random_init(o, px, py));
+        memcpy(o->sel, o->sel_next, HW * sizeof(uint32_t));
+        break;
+    case 5:
+        if (colour == 0) {
+            FOR_COLOUR(o, 0, if (RD(o, weak, py * o->W + px) != WEAK) k_sweep_strong(o, px, py, iter));
+        } else {
+            FOR_COLOUR(o, 1, if (RD(o, weak, py * o->W + px) != WEAK) k_sweep_strong(o, px, py, iter));
+        }
+        break;
+    case 6:
+        FOR_ALL(o, k_ransac_fit(o, px, py, iter));
+        break;
+    case 7:
+        FOR_ALL(o, k_local_refine(o, px, py));
+        break;
     default:
         st = APD_EINVAL;
+    }
+    if (st == APD_OK && stage >= 4) {
+        if (sel) memcpy(sel, o->sel, HW * sizeof(uint32_t));
+        if (costs) memcpy(costs, o->cost, HW * sizeof(float));
+        if (vw) memcpy(vw, o->vw, HW * (size_t)o->N);
+        if (fit) memcpy(fit, o->fit, HW * sizeof(f4));
     }
     if (st == APD_OK) {
         if (planes) memcpy(planes, o->plane, HW * sizeof(f4));
@@ -1884,6 +1961,35 @@ int oracle_kat_stage(const apd_problem *pb, int stage, const uint32_t *sel, cons
     }
     ctx_free(o);
     free(o);
+    return st;
+}
+
+int oracle_kat_stage(const apd_problem *pb, int stage, const uint32_t *sel, const float *costs, float *planes,
+                     uint8_t *weak, uint8_t *conf, int16_t *nearest, int16_t *anchors, uint8_t *reliable) {
+    if (stage < 0 || stage > 3) return APD_EINVAL; /* (sel and costs are inputs only for stages 0-3) */
+    return oracle_kat_stage_ex(pb, stage, 0, 0, (uint32_t *)sel, (float *)costs, planes, weak, conf, nearest, anchors,
+                               reliable, NULL, NULL);
+}
+
+/* The five (depth, normal) refinement candidates of PlaneHypothesisRefinementStrong (APD.cu:961-980)
+   for one pixel, RNG seed and current plane (sweep form): depths5, normals5x4 (x, y, z, 0). The draws
+   start a fresh stream of the pixel (the sweep's own follow its 15 view samples). */
+int oracle_refine_candidates(const apd_problem *pb, int px, int py, uint64_t seed, const float *plane4, float *depths5,
+                             float *normals20) {
+    octx *o = (octx *)malloc(sizeof(octx));
+    if (!o) return APD_ENOMEM;
+    int st = kat_ctx(o, pb);
+    if (st == APD_OK) {
+        f4 cur = {plane4[0], plane4[1], plane4[2], plane4[3]}, nc[5];
+        orng g;
+        orng_init(&g, seed, (uint32_t)(py * o->W + px), ORD_STRONG(0));
+        refine_candidates(o, px, py, &g, cur, depth_from_plane(&o->cam[0], cur, px, py), depths5, nc);
+        for (int k = 0; k < 5; ++k) {
+            normals20[4 * k] = nc[k].x; normals20[4 * k + 1] = nc[k].y; normals20[4 * k + 2] = nc[k].z;
+            normals20[4 * k + 3] = 0.0f;
+        }
+    }
+    ctx_free(o); free(o);
     return st;
 }
 

@@ -45,7 +45,27 @@ def load(path=None):
         f.argtypes = [C.c_float]
     lib.oracle_philox.restype = None
     lib.oracle_philox.argtypes = [C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32]
+    lib.oracle_run_staged.restype = C.c_int
+    lib.oracle_run_staged.argtypes = [C.POINTER(A.ApdProblem), C.POINTER(A.ApdOutputs), C.c_int, C.c_int, C.c_int]
+    # (pb, stage, iter, colour, sel, costs, planes, weak, conf, nearest, anchors, reliable, vw, fit)
+    lib.oracle_kat_stage_ex.restype = C.c_int
+    lib.oracle_kat_stage_ex.argtypes = [C.POINTER(A.ApdProblem), C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 10
+    lib.oracle_refine_candidates.restype = C.c_int
+    lib.oracle_refine_candidates.argtypes = [C.POINTER(A.ApdProblem), C.c_int, C.c_int, C.c_uint64,
+                                             C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]
     return lib
+
+
+def run_staged(lib, arrays: "A.ProblemArrays", n_iterations: int, do_finish: bool = False, nthreads: int = 0):
+    """The oracle's state after run_prepare and the first n_iterations sweep iterations (then
+    run_finish if do_finish). Mid-run planes are (reference-frame normal, distance to the origin)."""
+    pb = arrays.build()
+    hw = arrays.width * arrays.height
+    out = A.Outputs(arrays.width, arrays.height, len(arrays.images) - 1, max_weak=hw)
+    st = lib.oracle_run_staged(C.byref(pb), C.byref(out.struct()), n_iterations, int(do_finish), nthreads)
+    if st != 0:
+        raise RuntimeError(f"oracle_run_staged -> {st}")
+    return out
 
 
 def run(lib, arrays: "A.ProblemArrays", nthreads: int = 0, want_curve: bool = False):
