@@ -31,9 +31,11 @@ class OracleFusionView(C.Structure):
 
 
 def oracle():
-    if not os.path.exists(ORACLE_SO):
+    # APD_ORACLE_SO: a mutated oracle build (tools/mutate_oracle.py checks that the KATs reject it)
+    path = os.environ.get("APD_ORACLE_SO") or ORACLE_SO
+    if path == ORACLE_SO and not os.path.exists(path):
         subprocess.run(["make", "-C", os.path.dirname(ORACLE_SO)], check=True, capture_output=True)
-    lib = C.CDLL(ORACLE_SO)
+    lib = C.CDLL(path)
     lib.oracle_fusion.restype = C.c_int64
     lib.oracle_fusion.argtypes = [C.c_int, C.c_int, C.POINTER(OracleFusionView), C.c_int,
                                   C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
@@ -215,14 +217,7 @@ def oracle_candidates(views, ref, src_idx):
 def run_oracle(views, dataset, weak_filter):
     lib = oracle()
     n = len(views)
-    arr = (OracleFusionView * n)()
-    keep = []
-    for i, v in enumerate(views):
-        srcs = np.array(v["srcs"], np.int32)
-        keep.append(srcs)
-        arr[i] = OracleFusionView(v["depth"].shape[1], v["depth"].shape[0], v["cam"], v["depth"].ctypes.data,
-                                  v["normal"].ctypes.data, v["weak"].ctypes.data, v["conf"].ctypes.data,
-                                  v["bgr"].ctypes.data, v["ref"], len(srcs), srcs.ctypes.data)
+    arr, _keep = _oracle_views(views)
     skips = [np.zeros(v["depth"].shape, np.uint8) for v in views]
     skip_ptrs = (C.c_void_p * n)(*[s.ctypes.data for s in skips])
     cap = sum(v["depth"].size for v in views)

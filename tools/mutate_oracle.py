@@ -4,10 +4,13 @@ For each mutation below -- one reference rule or quirk restated wrongly -- build
 oracle/apd_oracle.c into a temporary liboracle.so and run the known-answer tests against it
 (APD_ORACLE_SO): the APD half's (MUTATIONS) against tests/test_oracle_kat_apd.py and
 tests/test_oracle_kat.py, the Strong half's (STRONG_MUTATIONS) against
-tests/test_oracle_kat_strong.py. A mutation the tests do not reject ("survived") marks a rule the
-KATs do not pin. Usage: python tools/mutate_oracle.py [--json apd.json] [--strong-json strong.json]
-[--only apd|strong]
+tests/test_oracle_kat_strong.py. FUSION_MUTATIONS mutate oracle/fusion_oracle.c instead and run
+tests/test_oracle_kat_fusion.py plus the oracle tests of tests/test_fusion.py. A mutation the tests
+do not reject ("survived") marks a rule the KATs do not pin. Usage: python tools/mutate_oracle.py
+[--json apd.json] [--strong-json strong.json] [--fusion-json fusion.json] [--only apd|strong|fusion]
+[--jobs N]
 """
+import concurrent.futures
 import json
 import os
 import subprocess
@@ -15,7 +18,7 @@ import sys
 import tempfile
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(REPO, "oracle", "apd_oracle.c")
+SOURCES = ("apd_oracle.c", "fusion_oracle.c")
 CFLAGS = "-O2 -mfma -mavx2 -fPIC -fopenmp -ffp-contract=off -fno-fast-math -std=c11 -w".split()
 
 MUTATIONS = [  # (name, reference lines, original text, mutated text)
@@ -127,48 +130,170 @@ STRONG_MUTATIONS = [
      "if ((double)(cost_now - min_cost) > 0.1) WR(o, plane, c).w = best;", "if ((double)(cost_now - min_cost) > 0.0) WR(o, plane, c).w = best;"),
 ]
 
+# depth-map fusion: oracle/fusion_oracle.c (every text is one rule of the helpers, WeakVisFilter,
+# RunFusion or the TAT variants; a text that occurs in several loops is mutated in all of them)
+_GEO_T = ("t.x = cam->R[0] * p.x + cam->R[3] * p.y + cam->R[6] * p.z;\n"
+          "    t.y = cam->R[1] * p.x + cam->R[4] * p.y + cam->R[7] * p.z;\n"
+          "    t.z = cam->R[2] * p.x + cam->R[5] * p.y + cam->R[8] * p.z;")
+_GEO_C = ("c.x = -(cam->R[0] * cam->t[0] + cam->R[3] * cam->t[1] + cam->R[6] * cam->t[2]);\n"
+          "    c.y = -(cam->R[1] * cam->t[0] + cam->R[4] * cam->t[1] + cam->R[7] * cam->t[2]);\n"
+          "    c.z = -(cam->R[2] * cam->t[0] + cam->R[5] * cam->t[1] + cam->R[8] * cam->t[2]);")
+_PROJ = ("float tx = cam->R[0] * X.x + cam->R[1] * X.y + cam->R[2] * X.z + cam->t[0];\n"
+         "    float ty = cam->R[3] * X.x + cam->R[4] * X.y + cam->R[5] * X.z + cam->t[1];\n"
+         "    float tz = cam->R[6] * X.x + cam->R[7] * X.y + cam->R[8] * X.z + cam->t[2];")
+
+
+def _transpose(text):
+    for a, b in (("R[1]", "R[3]"), ("R[2]", "R[6]"), ("R[5]", "R[7]")):
+        text = text.replace(a, "@").replace(b, a).replace("@", b)
+    return text
+
+
+_TAT_GATHER = ("f3 consistent_Point = PointX;\n                for (int j = 0; j < num_ngb; ++j) {\n"
+               "                    int src_index = index_of(n, v, v[i].src_ids[j]);")
+_RESET = "for (int j = 0; j < num_ngb; ++j) diff[j].dist = diff[j].depth = diff[j].angle = FLT_MAX;\n                "
+
+FUSION_MUTATIONS = [
+    ("Get3DPointonWorld: R instead of R^T on the point", "APD.cpp:875-877", _GEO_T, _transpose(_GEO_T)),
+    ("Get3DPointonWorld: R instead of R^T on t", "APD.cpp:881-883", _GEO_C, _transpose(_GEO_C)),
+    ("ProjectCamera: R^T instead of R", "APD.cpp:893-895", _PROJ, _transpose(_PROJ)),
+    ("ProjectCamera: - t", "APD.cpp:893-895", _PROJ, _PROJ.replace("+ cam->t", "- cam->t")),
+    ("Get3DPointonWorld: + R^T t", "APD.cpp:881-883", _GEO_C, _GEO_C.replace("= -(", "= (")),
+    ("ProjectCamera: K[1] dropped", "APD.cpp:898",
+     "cam->K[0] * tx + cam->K[1] * ty + cam->K[2] * tz", "cam->K[0] * tx + cam->K[2] * tz"),
+    ("Get3DPointonWorld: y over fx", "APD.cpp:871", "(y - cam->K[5]) / cam->K[4];", "(y - cam->K[5]) / cam->K[0];"),
+    ("Get3DPointonWorld: x about cy", "APD.cpp:870", "(x - cam->K[2]) / cam->K[0];", "(x - cam->K[5]) / cam->K[0];"),
+    ("rounding: + 0.5f dropped", "APD.cpp:999-1000,1173-1174",
+     "int_x86(py + 0.5f), src_c = int_x86(px + 0.5f)", "int_x86(py), src_c = int_x86(px)"),
+    ("rounding: truncation -> floor", "APD.cpp:999-1000,1173-1174", "return (int)v;", "return (int)floorf(v);"),
+    ("GetAngle: NaN -> 0 dropped", "APD.cpp:906-907", "if (angle != angle) return 0.0f;", "if (angle != angle) return 3.0f;"),
+    ("RunFusion: reprojection cut 2.0 -> 1.5", "APD.cpp:1189", "reproj_error < 2.0f &&", "reproj_error < 1.5f &&"),
+    ("RunFusion: relative depth cut 0.01 -> 0.008", "APD.cpp:1189",
+     "relative_depth_diff < 0.01f &&", "relative_depth_diff < 0.008f &&"),
+    ("RunFusion: relative depth cut 0.01 -> 0.012", "APD.cpp:1189",
+     "relative_depth_diff < 0.01f &&", "relative_depth_diff < 0.012f &&"),
+    ("RunFusion: angle cut 0.174533 -> 0.15", "APD.cpp:1189", "angle < 0.174533f)", "angle < 0.15f)"),
+    ("RunFusion: angle cut 0.174533 -> 0.2", "APD.cpp:1189", "angle < 0.174533f)", "angle < 0.2f)"),
+    ("RunFusion: 200 * rel -> 100 * rel", "APD.cpp:1192", "200 * relative_depth_diff", "100 * relative_depth_diff"),
+    ("RunFusion: angle * 10 dropped", "APD.cpp:1192", " + angle * 10;", ";"),
+    ("RunFusion: 0.45 / 0.3 swapped", "APD.cpp:1198", "== WEAK ? 0.45f : 0.3f", "== WEAK ? 0.3f : 0.45f"),
+    ("RunFusion: colour / n instead of / (n + 1)", "APD.cpp:1215-1217", "/= (num_consistent + 1);", "/= (num_consistent);"),
+    ("RunFusion: n >= 1 -> n >= 2", "APD.cpp:1199", "num_consistent >= 1 &&", "num_consistent >= 2 &&"),
+    ("RunFusion: source masks not written", "APD.cpp:1209",
+     "masks[src_index][(size_t)used_r[j] * v[src_index].width + used_c[j]] = 1;", ""),
+    ("RunFusion: masked reference pixel not skipped", "APD.cpp:1149", "if (masks[ref_index][p] == 1) continue;", ""),
+    ("masked source pixel not skipped", "APD.cpp:1176,1370,1569", "if (masks[src_index][sp] == 1) continue;", ""),
+    ("RunFusion: filtered pixel not skipped", "APD.cpp:1152",
+     "if (masks[ref_index][p] == 1) continue;\n                if (skip[ref_index][p] == 1) continue;",
+     "if (masks[ref_index][p] == 1) continue;"),
+    ("source depth <= 0 -> < 0", "APD.cpp:1179,1373,1572", "if (src_depth <= 0.0) continue;", "if (src_depth < 0.0) continue;"),
+    ("NaN reference depth skipped", "APD.cpp:1157,1354,1550", "if (ref_depth <= 0.0) continue;", "if (!(ref_depth > 0.0)) continue;"),
+    ("filter: STRONG reference pixels flagged too", "APD.cpp:977",
+     "if (v[ref_index].weak[(size_t)r * width + c] != WEAK) continue;", "if (v[ref_index].weak[(size_t)r * width + c] == 2) continue;"),
+    ("filter: view angle 80 -> 90 degrees", "APD.cpp:991", "if (angle > 80.0f) continue;", "if (angle > 90.0f) continue;"),
+    ("filter: view angle in radians", "APD.cpp:990", "angle = (float)(angle * 180.0f / M_PI);", ""),
+    ("filter: proj_depth <= 0 let through", "APD.cpp:997", "if (proj_depth <= 0.0f) continue;", ""),
+    ("filter: occlusion margin 0.01 -> 0.02", "APD.cpp:1006,1012", "src_depth - 0.01f * src_depth", "src_depth - 0.02f * src_depth"),
+    ("filter: occlusion margin dropped", "APD.cpp:1006,1012", "src_depth - 0.01f * src_depth", "src_depth"),
+    ("filter: strong >= 2 -> >= 3", "APD.cpp:1019", "strong_occluded >= 2", "strong_occluded >= 3"),
+    ("filter: weak >= 4 -> >= 3", "APD.cpp:1019", "weak_occluded >= 4", "weak_occluded >= 3"),
+    ("filter: weak >= 4 -> >= 5", "APD.cpp:1019", "weak_occluded >= 4", "weak_occluded >= 5"),
+    ("filter: confidence compare reversed", "APD.cpp:1010-1011",
+     "conf_at_float(&v[src_index], src_r, src_c) < conf_at_float(&v[ref_index], r, c)",
+     "conf_at_float(&v[src_index], src_r, src_c) > conf_at_float(&v[ref_index], r, c)"),
+    ("filter: confidence compare <=", "APD.cpp:1010-1011",
+     "conf_at_float(&v[src_index], src_r, src_c) < conf_at_float(&v[ref_index], r, c)",
+     "conf_at_float(&v[src_index], src_r, src_c) <= conf_at_float(&v[ref_index], r, c)"),
+    ("filter: STRONG source needs the confidence test too", "APD.cpp:1005-1008",
+     "if (proj_depth < src_depth - 0.01f * src_depth) strong_occluded++;",
+     "if (conf_at_float(&v[src_index], src_r, src_c) < conf_at_float(&v[ref_index], r, c) && "
+     "proj_depth < src_depth - 0.01f * src_depth) strong_occluded++;"),
+    ("filter: confidence read at column c, not 4c", "APD.cpp:1010-1011",
+     "(size_t)r * v->width + 4 * (size_t)c;", "(size_t)r * v->width + (size_t)c;"),
+    ("filter: confidence read as a byte", "APD.cpp:1010-1011",
+     "float f;\n    memcpy(&f, &u, 4);\n    return f;", "return (float)b[0];"),
+    ("filter: bytes past the confidence map are 0x7f", "APD.cpp:1010-1011", "v->confidence[o + k] : 0;", "v->confidence[o + k] : 0x7f;"),
+    ("filter: state 2 counted as WEAK", "APD.cpp:1009", "} else if (v[src_index].weak[sp] == WEAK) {", "} else {"),
+    ("TAT: cost cache reset per pixel", "APD.cpp:1347,1541", _TAT_GATHER, _RESET + _TAT_GATHER),
+    ("TAT_A: colours averaged like TAT_I", "APD.cpp:1596",
+     "if (variant == 1) {\n                            for (int j = 0; j < num_ngb; ++j) {", "if (1) {\n                            for (int j = 0; j < num_ngb; ++j) {"),
+    ("TAT_I: reference colour alone like TAT_A", "APD.cpp:1404-1417",
+     "if (variant == 1) {\n                            for (int j = 0; j < num_ngb; ++j) {", "if (0) {\n                            for (int j = 0; j < num_ngb; ++j) {"),
+    ("TAT: count >= k -> count > k", "APD.cpp:1399,1593", "if (count >= k) {", "if (count > k) {"),
+    ("TAT: depth_base swapped between the variants", "APD.cpp:1240,1444",
+     "variant == 1 ? 1.0f / 3500.0f : 1.0f / 3000.0f", "variant == 1 ? 1.0f / 3000.0f : 1.0f / 3500.0f"),
+    ("TAT: dist_base 0.25 -> 0.3", "APD.cpp:1239,1443", "const float dist_base = 0.25f;", "const float dist_base = 0.3f;"),
+    ("TAT: levels start at k = 1", "APD.cpp:1389,1586", "for (int k = 2; k <= num_ngb; ++k) {", "for (int k = 1; k <= num_ngb; ++k) {"),
+    ("TAT: levels stop at k = n - 1", "APD.cpp:1389,1586", "for (int k = 2; k <= num_ngb; ++k) {", "for (int k = 2; k < num_ngb; ++k) {"),
+    ("TAT_A: angle cut applied as in TAT_I", "APD.cpp:1589", "if (variant == 1) pass = pass &&", "if (1) pass = pass &&"),
+    ("TAT_I: angle cut dropped", "APD.cpp:1393-1394", "if (variant == 1) pass = pass &&", "if (0) pass = pass &&"),
+    ("TAT_I: angle cut without angle_base", "APD.cpp:1394", "(k * angle_grad + angle_base)", "(k * angle_grad)"),
+    ("TAT: masks[ref] not set", "APD.cpp:1422,1598", "masks[ref_index][p] = 1;", ""),
+    ("TAT_A: skip_weak not counted", "APD.cpp:1546", "skip_weak++;", ""),
+    ("TAT: levels tried from the top (the widest level wins, not the first)", "APD.cpp:1389,1586",
+     "for (int k = 2; k <= num_ngb; ++k) {", "for (int k = num_ngb; k >= 2; --k) {"),
+    ("index_of: a missing id reads as the last view", "APD.cpp:1143,1167", "return i;\n    return 0;", "return i;\n    return n - 1;"),
+    ("index_of: last index of a repeated id", "APD.cpp:1091",
+     "for (int i = 0; i < n; ++i)\n        if (v[i].ref_id == id) return i;", "for (int i = n - 1; i >= 0; --i)\n        if (v[i].ref_id == id) return i;"),
+    ("RunFusion: the problem's own view instead of index_of(ref id)", "APD.cpp:1143",
+     "int ref_index = index_of(n, v, v[i].ref_id);", "int ref_index = i;"),
+]
+
 TESTS = ["tests/test_oracle_kat_apd.py", "tests/test_oracle_kat.py"]
 STRONG_TESTS = ["tests/test_oracle_kat_strong.py"]
+FUSION_TESTS = ["tests/test_oracle_kat_fusion.py", "tests/test_fusion.py::test_oracle_runfusion_known_answer",
+                "tests/test_fusion.py::test_oracle_tat_known_answer",
+                "tests/test_fusion.py::test_oracle_weak_filter_only_flags_weak"]
 
 
-def run_set(mutations, tests):
-    src = open(SRC).read()
-    results = []
+def run_set(mutations, tests, target="apd_oracle.c", jobs=1):
+    """Mutates oracle/<target>; the other oracle source is compiled unchanged into every build."""
+    src = open(os.path.join(REPO, "oracle", target)).read()
+    other = [os.path.join(REPO, "oracle", f) for f in SOURCES if f != target]
     with tempfile.TemporaryDirectory() as td:
         os.symlink(os.path.join(REPO, "include"), os.path.join(td, "include"))  # the source's ../include
-        for name, ref, old, new in mutations:
-            n = src.count(old)
-            if n == 0:
-                results.append({"mutation": name, "ref": ref, "status": "NOT APPLIED (text not found)"})
-                continue
-            mdir = os.path.join(td, "oracle")
-            os.makedirs(mdir, exist_ok=True)
-            csrc = os.path.join(mdir, "apd_oracle.c")
+        env0 = dict(os.environ, APD_FUSION_KAT_CACHE=os.path.join(td, "kat_cache"))
+        if target == "fusion_oracle.c":  # construct the problems once, with the unmutated oracle
+            subprocess.run([sys.executable, "-m", "pytest", "-q", "-p", "no:cacheprovider", tests[0], "-k",
+                            "test_construction_is_guarded"], cwd=REPO, env=env0, check=True, capture_output=True)
+
+        def one(k):
+            name, ref, old, new = mutations[k]
+            if src.count(old) == 0:
+                return {"mutation": name, "ref": ref, "status": "NOT APPLIED (text not found)"}
+            mdir = os.path.join(td, f"m{k}", "oracle")
+            os.makedirs(mdir)
+            os.symlink(os.path.join(REPO, "include"), os.path.join(td, f"m{k}", "include"))
+            csrc = os.path.join(mdir, target)
             open(csrc, "w").write(src.replace(old, new))
-            so = os.path.join(td, "liboracle_mut.so")
-            inc = os.path.join(REPO, "include")
-            subprocess.run(["gcc", *CFLAGS, "-I", inc, "-shared", "-o", so, csrc,
-                            os.path.join(REPO, "oracle", "fusion_oracle.c"), "-lm"], check=True,
-                           cwd=os.path.join(REPO, "oracle"))
-            env = dict(os.environ, APD_ORACLE_SO=so)
+            so = os.path.join(td, f"liboracle_mut{k}.so")
+            subprocess.run(["gcc", *CFLAGS, "-I", os.path.join(REPO, "include"), "-shared", "-o", so, csrc, *other, "-lm"],
+                           check=True, cwd=os.path.join(REPO, "oracle"))
             r = subprocess.run([sys.executable, "-m", "pytest", "-x", "-q", "-p", "no:cacheprovider", *tests],
-                               cwd=REPO, env=env, capture_output=True, text=True)
-            killed = r.returncode != 0
+                               cwd=REPO, env=dict(env0, APD_ORACLE_SO=so), capture_output=True, text=True)
             first = next((ln for ln in r.stdout.splitlines() if ln.startswith("FAILED")), "")
-            results.append({"mutation": name, "ref": ref, "status": "killed" if killed else "SURVIVED",
-                            "by": first.replace("FAILED ", "")[:120]})
+            if r.returncode != 0 and not first:  # a collection or fixture ERROR rejects nothing
+                raise RuntimeError(f"pytest ended with {r.returncode} and no FAILED line:\n{r.stdout[-2000:]}")
+            killed = bool(first)
             print(f"{'killed  ' if killed else 'SURVIVED'}  {name}  ({ref})  {first[7:90]}", flush=True)
-    return results
+            return {"mutation": name, "ref": ref, "status": "killed" if killed else "SURVIVED",
+                    "by": first.replace("FAILED ", "")[:120]}
+
+        with concurrent.futures.ThreadPoolExecutor(max(1, jobs)) as pool:
+            return list(pool.map(one, range(len(mutations))))
 
 
 def main():
     only = sys.argv[sys.argv.index("--only") + 1] if "--only" in sys.argv else None
+    jobs = int(sys.argv[sys.argv.index("--jobs") + 1]) if "--jobs" in sys.argv else min(8, os.cpu_count() or 1)
     bad = 0
-    for half, flag, mutations, tests in (("apd", "--json", MUTATIONS, TESTS),
-                                         ("strong", "--strong-json", STRONG_MUTATIONS, STRONG_TESTS)):
+    for half, flag, mutations, tests, target in (
+            ("apd", "--json", MUTATIONS, TESTS, "apd_oracle.c"),
+            ("strong", "--strong-json", STRONG_MUTATIONS, STRONG_TESTS, "apd_oracle.c"),
+            ("fusion", "--fusion-json", FUSION_MUTATIONS, FUSION_TESTS, "fusion_oracle.c")):
         if only not in (None, half):
             continue
-        results = run_set(mutations, tests)
+        results = run_set(mutations, tests, target, jobs)
         if flag in sys.argv:
             with open(sys.argv[sys.argv.index(flag) + 1], "w") as fh:
                 json.dump(results, fh, indent=1)
