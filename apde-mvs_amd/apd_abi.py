@@ -265,6 +265,14 @@ PREP_CAMERA_MODELS = {"SIMPLE_PINHOLE": (0, 3), "PINHOLE": (1, 4), "SIMPLE_RADIA
                       "OPENCV": (4, 8), "OPENCV_FISHEYE": (5, 8), "FULL_OPENCV": (6, 12),
                       "SIMPLE_RADIAL_FISHEYE": (8, 4), "RADIAL_FISHEYE": (9, 5), "THIN_PRISM_FISHEYE": (10, 12)}
 PREP_MAX_IMAGES = 16384
+# include/apd_seg.h: flat-zone sa_masks. A list of its own; EXPORTS, EVAL_EXPORTS and PREP_EXPORTS stay as they are
+SEG_EXPORTS = ["apd_seg_create", "apd_seg_destroy", "apd_seg_last_error", "apd_seg_flat_zones_bgr8",
+               "apd_seg_label_mask", "apd_seg_get_stage", "apd_seg_get_timing", "apd_seg_flat_zones_bgr8_host",
+               "apd_seg_label_mask_host", "apd_seg_working_size", "apd_seg_label_colour"]
+SEG_STAGES = {"work": 0, "smooth": 1, "flat": 2, "roots": 3, "areas": 4}
+SEG_TIMES = ["upload_ms", "downscale_ms", "smooth_flat_ms", "ccl_tile_ms", "ccl_merge_ms", "flatten_area_ms",
+             "rank_ms", "relabel_ms", "download_ms"]
+SEG_MAX_LABELS = 255
 PREP_ATOMICS_DEFAULT, PREP_ATOMICS_GLOBAL, PREP_ATOMICS_LDS = 0, 1, 2
 
 
@@ -494,6 +502,32 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     lib.apd_prep_undistort_xy.restype = C.c_int32
     lib.apd_prep_undistort_xy.argtypes = [C.c_int32, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p,
                                           C.POINTER(C.c_int64)]
+    # include/apd_seg.h
+    lib.apd_seg_create.restype = C.c_void_p
+    lib.apd_seg_create.argtypes = [C.c_int32]
+    lib.apd_seg_destroy.argtypes = [C.c_void_p]
+    lib.apd_seg_last_error.restype = C.c_char_p
+    lib.apd_seg_last_error.argtypes = [C.c_void_p]
+    i32p = C.POINTER(C.c_int32)
+    lib.apd_seg_flat_zones_bgr8.restype = C.c_int32
+    lib.apd_seg_flat_zones_bgr8.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32,
+                                            C.c_int32, C.c_void_p, i32p, i32p, i32p, i32p]
+    lib.apd_seg_label_mask.restype = C.c_int32
+    lib.apd_seg_label_mask.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
+    lib.apd_seg_get_stage.restype = C.c_int32
+    lib.apd_seg_get_stage.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
+    lib.apd_seg_get_timing.restype = C.c_int32
+    lib.apd_seg_get_timing.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
+    lib.apd_seg_flat_zones_bgr8_host.restype = C.c_int32
+    lib.apd_seg_flat_zones_bgr8_host.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
+                                                 C.c_void_p, i32p, i32p, i32p, i32p, C.c_void_p, C.c_void_p,
+                                                 C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.apd_seg_label_mask_host.restype = C.c_int32
+    lib.apd_seg_label_mask_host.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
+    lib.apd_seg_working_size.restype = C.c_int32
+    lib.apd_seg_working_size.argtypes = [C.c_int32, C.c_int32, C.c_int32, i32p, i32p, i32p]
+    lib.apd_seg_label_colour.restype = None
+    lib.apd_seg_label_colour.argtypes = [C.c_int32, C.c_void_p]
     return lib
 
 
@@ -1318,6 +1352,151 @@ class PrepEngine:
     def close(self):
         if self.ctx:
             self.lib.apd_prep_destroy(self.ctx)
+            self.ctx = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def seg_threshold_q8(threshold: float) -> int:
+    """A threshold in grey levels -> include/apd_seg.h's units of 1/256 level."""
+    return int(round(256 * threshold))
+
+
+def seg_working_size(w: int, h: int, max_size: int = 2560, lib: Optional[C.CDLL] = None):
+    """apd_seg_working_size: (s, W, H) of the contract's stage 1."""
+    s, W, H = C.c_int32(), C.c_int32(), C.c_int32()
+    st = (lib or load_library()).apd_seg_working_size(w, h, max_size, C.byref(s), C.byref(W), C.byref(H))
+    if st != 0:
+        raise ApdError(f"apd_seg_working_size -> {STATUS.get(st, st)}")
+    return s.value, W.value, H.value
+
+
+def seg_label_colour(k: int, lib: Optional[C.CDLL] = None):
+    """apd_seg_label_colour: (B, G, R) of label k in apd_segment's picture."""
+    bgr = (C.c_uint8 * 3)()
+    (lib or load_library()).apd_seg_label_colour(k, bgr)
+    return tuple(bgr)
+
+
+def _seg_image(bgr):
+    """(h, w, 3) uint8, numpy or torch (kept where it is), contiguous"""
+    src = _keep(bgr, np.uint8)
+    if src.ndim != 3 or src.shape[2] != 3:
+        raise ValueError("bgr is (h, w, 3) uint8")
+    return src
+
+
+def seg_flat_zones_host(bgr, max_size: int = 2560, threshold: float = 1.0, min_area: int = 256, stages: bool = False,
+                        lib: Optional[C.CDLL] = None):
+    """apd_seg_flat_zones_bgr8_host: the five stages of include/apd_seg.h on the CPU. bgr (h, w, 3) uint8 ->
+    (labels (H, W) uint8, n_survivors, n_labels); with stages=True a fourth entry, the dict of work (H, W, 3)
+    uint8, smooth (3, H, W) uint16, flat (H, W) uint8, roots and areas (H, W) int32."""
+    lib = lib or load_library()
+    src = np.ascontiguousarray(_seg_image(bgr))
+    h, w = src.shape[:2]
+    _, W, H = seg_working_size(w, h, max_size, lib)
+    labels = np.empty((H, W), np.uint8)
+    st_arrays = {"work": np.empty((H, W, 3), np.uint8), "smooth": np.empty((3, H, W), np.uint16),
+                 "flat": np.empty((H, W), np.uint8), "roots": np.empty((H, W), np.int32),
+                 "areas": np.empty((H, W), np.int32)} if stages else {}
+    ow, oh, ns, nl = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32()
+    st = lib.apd_seg_flat_zones_bgr8_host(w, h, src.ctypes.data, max_size, seg_threshold_q8(threshold), min_area,
+                                          labels.ctypes.data, C.byref(ow), C.byref(oh), C.byref(ns), C.byref(nl),
+                                          *[st_arrays[k].ctypes.data if stages else None for k in SEG_STAGES])
+    if st != 0:
+        raise ApdError(f"apd_seg_flat_zones_bgr8_host -> {STATUS.get(st, st)}")
+    assert (ow.value, oh.value) == (W, H)
+    return (labels, ns.value, nl.value, st_arrays) if stages else (labels, ns.value, nl.value)
+
+
+def seg_label_mask_host(mask, lib: Optional[C.CDLL] = None) -> np.ndarray:
+    """apd_seg_label_mask_host: (H, W) mask, non-zero = set -> (H, W) int32 roots (the smallest linear index
+    of the pixel's 4-connected component), -1 where the mask is 0."""
+    m = np.ascontiguousarray(mask, np.uint8)
+    if m.ndim != 2:
+        raise ValueError("mask is (H, W)")
+    roots = np.empty(m.shape, np.int32)
+    st = (lib or load_library()).apd_seg_label_mask_host(m.shape[1], m.shape[0], m.ctypes.data, roots.ctypes.data)
+    if st != 0:
+        raise ApdError(f"apd_seg_label_mask_host -> {STATUS.get(st, st)}")
+    return roots
+
+
+class SegEngine:
+    """One apd_seg_ctx (include/apd_seg.h): flat-zone sa_masks on the device. Images and masks are numpy
+    arrays or torch tensors; a CUDA tensor is read in place and answered with CUDA tensors."""
+
+    def __init__(self, device: int = 0, lib: Optional[C.CDLL] = None):
+        self.lib = lib or load_library()
+        self.device = device
+        self.shape = None  # (H, W) of the last call
+        self.ctx = self.lib.apd_seg_create(device)
+        if not self.ctx:
+            raise ApdError("apd_seg_create failed: " + (self.lib.apd_seg_last_error(None) or b"?").decode())
+
+    def _check(self, st: int, what: str):
+        if st != 0:
+            msg = (self.lib.apd_seg_last_error(self.ctx) or b"").decode()
+            raise ApdError(f"{what} -> {STATUS.get(st, st)}: {msg}")
+
+    @staticmethod
+    def _empty(like, shape, dtype):
+        if hasattr(like, "is_cuda") and like.is_cuda:
+            import torch
+            return torch.empty(shape, dtype=getattr(torch, _TORCH_DTYPES[np.dtype(dtype)]), device=like.device)
+        return np.empty(shape, dtype)
+
+    def flat_zones(self, bgr, max_size: int = 2560, threshold: float = 1.0, min_area: int = 256):
+        """apd_seg_flat_zones_bgr8: bgr (h, w, 3) uint8 -> (labels (H, W) uint8, n_survivors, n_labels)."""
+        src = _seg_image(bgr)
+        h, w = int(src.shape[0]), int(src.shape[1])
+        _, W, H = seg_working_size(w, h, max_size, self.lib)
+        labels = self._empty(src, (H, W), np.uint8)
+        _torch_device_sync(src, labels)
+        ow, oh, ns, nl = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32()
+        self._check(self.lib.apd_seg_flat_zones_bgr8(self.ctx, w, h, _ptr(src, C.c_uint8), max_size,
+                                                     seg_threshold_q8(threshold), min_area, _ptr(labels, C.c_uint8),
+                                                     C.byref(ow), C.byref(oh), C.byref(ns), C.byref(nl)),
+                    "apd_seg_flat_zones_bgr8")
+        self.shape = (oh.value, ow.value)
+        return labels, ns.value, nl.value
+
+    def label_mask(self, mask):
+        """apd_seg_label_mask: (H, W) mask, non-zero = set -> (H, W) int32 roots, -1 where the mask is 0."""
+        m = _keep(mask, np.uint8)
+        if m.ndim != 2:
+            raise ValueError("mask is (H, W)")
+        H, W = int(m.shape[0]), int(m.shape[1])
+        roots = self._empty(m, (H, W), np.int32)
+        _torch_device_sync(m, roots)
+        self._check(self.lib.apd_seg_label_mask(self.ctx, W, H, _ptr(m, C.c_uint8), _ptr(roots, C.c_int32)),
+                    "apd_seg_label_mask")
+        self.shape = (H, W)
+        return roots
+
+    def stage(self, name: str) -> np.ndarray:
+        """apd_seg_get_stage of the last call: "work", "smooth", "flat", "roots" or "areas" as numpy."""
+        if name not in SEG_STAGES:
+            raise ValueError(f"stage is one of {list(SEG_STAGES)}")
+        H, W = self.shape or (1, 1)
+        shape, dtype = {"work": ((H, W, 3), np.uint8), "smooth": ((3, H, W), np.uint16), "flat": ((H, W), np.uint8),
+                        "roots": ((H, W), np.int32), "areas": ((H, W), np.int32)}[name]
+        out = np.empty(shape, dtype)
+        self._check(self.lib.apd_seg_get_stage(self.ctx, SEG_STAGES[name], out.ctypes.data), "apd_seg_get_stage")
+        return out
+
+    def timing(self) -> dict:
+        ms = (C.c_double * len(SEG_TIMES))()
+        self._check(self.lib.apd_seg_get_timing(self.ctx, ms), "apd_seg_get_timing")
+        return dict(zip(SEG_TIMES, [float(v) for v in ms]))
+
+    def close(self):
+        if self.ctx:
+            self.lib.apd_seg_destroy(self.ctx)
             self.ctx = None
 
     def __del__(self):

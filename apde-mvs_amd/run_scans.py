@@ -8,6 +8,9 @@ and the same per-scan command it emits (run.py:104-119), so a maintainer can poi
   * SAM mask generation (tools/run_SAM.py) is out of scope (a learned model with network
     checkpoints): scans without sa_masks/ run like the reference binary does when the folder is
     missing (it logs "Can't find sa mask folder" and runs without SA).
+    With --flat_zone_masks (new, opt-in) such a scan first gets sa_masks/ from `apd_segment` (next to
+    the apd binary): flat-zone labels, include/apd_seg.h. They are not SAM masks, and what they do
+    to a reconstruction of a real scene is unmeasured. Without the flag nothing changes.
   * --gpus_per_scan K (new): hand K devices to each scan (`apd --gpus a,b,..`, Jacobi passes
     sharded over the devices), for batches with fewer scans than GPUs.
   * --backup_code is not restated (it copies the reference's CUDA sources).
@@ -46,6 +49,8 @@ def parse_args(argv=None):
                  'flush', 'ETH3D_train', 'ETH3D_test', 'TaT_intermediate', 'TaT_advanced', 'export_anchor',
                  'export_curve', 'no_image_symlink', 'review'):
         p.add_argument('--' + flag, action='store_true', default=False)
+    # absent from the namespace unless given, so that the printed arguments stay what they were
+    p.add_argument('--flat_zone_masks', action='store_true', default=argparse.SUPPRESS)
     p.add_argument('--image_dir_name', type=str, nargs='+', default=['images', 'undist/images'])
     p.add_argument('--image_suffixes', type=str, nargs='+', default=['.jpg', '.jpeg', '.png'])
     return p.parse_args(argv)
@@ -96,6 +101,12 @@ def dataset_of(data_dir, scan):
     return 'General'
 
 
+def segment_command(args, scan_dir, gpus):
+    """`apd_segment` on a scan, from the directory of the apd binary, on the scan's first device"""
+    return '{} --dense_folder {} --device {}'.format(os.path.join(os.path.dirname(args.APD_path), 'apd_segment'), scan_dir,
+                                                     gpus[0])
+
+
 def apd_command(args, scan_dir, gpus, dataset):
     """The per-scan command of run.py:104-119 (`--gpus` added when a scan gets several devices)."""
     tf = lambda b: 'true' if b else 'false'
@@ -136,7 +147,11 @@ def worker(args, scan):
         k = max(1, args.gpus_per_scan)
         first = (pos // args.work_num) * k
         gpus = list(range(first, first + k))
-        if not args.no_sam and not os.path.isdir(os.path.join(scan_dir, 'sa_masks')):
+        segment = None
+        if not args.no_sam and not os.path.isdir(os.path.join(scan_dir, 'sa_masks')) and \
+                getattr(args, 'flat_zone_masks', False):
+            segment = segment_command(args, scan_dir, gpus)
+        elif not args.no_sam and not os.path.isdir(os.path.join(scan_dir, 'sa_masks')):
             print('[{}] no sa_masks/ (SAM generation is out of scope): running without SA masks'.format(scan), flush=True)
         apd_dir = os.path.join(scan_dir, 'APD')
         os.makedirs(apd_dir, exist_ok=True)
@@ -148,9 +163,17 @@ def worker(args, scan):
             return 0
         # one write per line: print() writes the text and the newline separately, and two slots
         # printing at once could put two commands on one line
+        if segment:
+            segment += ' >> ' + os.path.join(apd_dir, 'segment_log.txt')
+            print(segment + '\n', end='', flush=True)
         print(cmd + '\n', end='', flush=True)
         if args.review:
             return 0
+        if segment:
+            rc = subprocess.run(segment, shell=True).returncode
+            if rc != 0:
+                print('[{}] apd_segment failed with exit code {}'.format(scan, rc), flush=True)
+                return rc
         return subprocess.run(cmd, shell=True).returncode
     finally:
         with _lock:
