@@ -352,6 +352,8 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     lib.apd_device_free.argtypes = [C.c_void_p, C.c_void_p]
     lib.apd_device_copy.restype = C.c_int32
     lib.apd_device_copy.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
+    lib.apd_device_bytes.restype = C.c_int32
+    lib.apd_device_bytes.argtypes = [C.c_void_p, C.POINTER(C.c_size_t)]
     lib.apd_device_mem_info.restype = C.c_int32
     lib.apd_device_mem_info.argtypes = [C.c_void_p, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
     lib.apd_device_resize_nearest.restype = C.c_int32
@@ -531,19 +533,41 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     return lib
 
 
-class FusionEngine:
-    """One apd_fusion_ctx (include/apd_fusion.h) with its views resident on the device."""
+class _Context:
+    """What the five engine classes share: one device context of the library, made by
+    <PREFIX>_create, asked by <PREFIX>_last_error and given back by <PREFIX>_destroy."""
+
+    PREFIX = ""
 
     def __init__(self, device: int = 0, lib: Optional[C.CDLL] = None):
         self.lib = lib or load_library()
-        self.ctx = self.lib.apd_fusion_create(device)
+        self.device = device
+        self._last_error = getattr(self.lib, self.PREFIX + "_last_error")
+        self.ctx = getattr(self.lib, self.PREFIX + "_create")(device)
         if not self.ctx:
-            raise ApdError("apd_fusion_create failed: " + (self.lib.apd_fusion_last_error(None) or b"?").decode())
+            raise ApdError(f"{self.PREFIX}_create failed: " + (self._last_error(None) or b"?").decode())
 
     def _check(self, st: int, what: str):
         if st != 0:
-            msg = (self.lib.apd_fusion_last_error(self.ctx) or b"").decode()
+            msg = (self._last_error(self.ctx) or b"").decode()
             raise ApdError(f"{what} -> {STATUS.get(st, st)}: {msg}")
+
+    def close(self):
+        if self.ctx:
+            getattr(self.lib, self.PREFIX + "_destroy")(self.ctx)
+            self.ctx = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class FusionEngine(_Context):
+    """One apd_fusion_ctx (include/apd_fusion.h) with its views resident on the device."""
+
+    PREFIX = "apd_fusion"
 
     def set_views(self, views):
         """views: dicts with depth (H,W) f32, normal (H,W,3) f32, weak/conf (H,W) u8, cam ApdCamera."""
@@ -579,18 +603,6 @@ class FusionEngine:
                                                    None if qk is None else qk.ctypes.data, pix.ctypes.data,
                                                    lv.ctypes.data), "apd_fusion_tat_levels")
         return pix, lv
-
-    def close(self):
-        if self.ctx:
-            self.lib.apd_fusion_destroy(self.ctx)
-            self.ctx = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 ETH3D_TOLERANCES = (0.01, 0.02, 0.05, 0.1, 0.2, 0.5)  # the ones tools/eval_eth_train.py passes
 
@@ -785,7 +797,7 @@ def masked_stats_host(dist, flag, limit: float, lib: Optional[C.CDLL] = None) ->
     return {"count": c.value, "sum": s.value, "median": m.value}
 
 
-class EvalEngine:
+class EvalEngine(_Context):
     """One apd_eval_ctx (include/apd_eval.h): truncated nearest-neighbour distances to a target cloud,
     voxel down-sampling, z-buffer rendering and visibility, free gaps and voxel scores, crop volume,
     nearest neighbour with index, transform and ICP registration, radius thinning, observability mask,
@@ -793,17 +805,7 @@ class EvalEngine:
     torch tensors on the context's device (results come back as tensors there; torch's current
     stream is waited for first, as for every device input of this library)."""
 
-    def __init__(self, device: int = 0, lib: Optional[C.CDLL] = None):
-        self.lib = lib or load_library()
-        self.device = device
-        self.ctx = self.lib.apd_eval_create(device)
-        if not self.ctx:
-            raise ApdError("apd_eval_create failed: " + (self.lib.apd_eval_last_error(None) or b"?").decode())
-
-    def _check(self, st: int, what: str):
-        if st != 0:
-            msg = (self.lib.apd_eval_last_error(self.ctx) or b"").decode()
-            raise ApdError(f"{what} -> {STATUS.get(st, st)}: {msg}")
+    PREFIX = "apd_eval"
 
     @staticmethod
     def _cloud(xyz):
@@ -1205,18 +1207,6 @@ class EvalEngine:
                     "apd_eval_get_dtu_timing")
         return {"mask_ms": m.value, "half_space_ms": h.value, "stats_ms": s.value}
 
-    def close(self):
-        if self.ctx:
-            self.lib.apd_eval_destroy(self.ctx)
-            self.ctx = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
 def prep_cos_gate(degrees: float = 1.0, lib: Optional[C.CDLL] = None) -> float:
     """apd_prep_cos_gate: the smallest double q with (180/pi)*acos(q) < degrees. Host only."""
     return float((lib or load_library()).apd_prep_cos_gate(float(degrees)))
@@ -1273,22 +1263,12 @@ def prep_undistort_xy(xy, model, params, lib: Optional[C.CDLL] = None):
     return out, int(bad.value)
 
 
-class PrepEngine:
+class PrepEngine(_Context):
     """One apd_prep_ctx (include/apd_prep.h): pair counts by tracks and per-image depth order
     statistics of a sparse model. All arrays are numpy, in the layout of apd_prep_set_model."""
 
-    def __init__(self, device: int = 0, lib: Optional[C.CDLL] = None):
-        self.lib = lib or load_library()
-        self.device = device
-        self.n_images = 0
-        self.ctx = self.lib.apd_prep_create(device)
-        if not self.ctx:
-            raise ApdError("apd_prep_create failed: " + (self.lib.apd_prep_last_error(None) or b"?").decode())
-
-    def _check(self, st: int, what: str):
-        if st != 0:
-            msg = (self.lib.apd_prep_last_error(self.ctx) or b"").decode()
-            raise ApdError(f"{what} -> {STATUS.get(st, st)}: {msg}")
+    PREFIX = "apd_prep"
+    n_images = 0
 
     def set_model(self, rot, trans, centres, xyz, obs_offset, obs_point):
         r = np.ascontiguousarray(rot, np.float64).reshape(-1)
@@ -1348,18 +1328,6 @@ class PrepEngine:
         self._check(self.lib.apd_prep_get_undistort_timing(self.ctx, C.byref(a), C.byref(b), C.byref(c)),
                     "apd_prep_get_undistort_timing")
         return {"upload_ms": a.value, "kernel_ms": b.value, "download_ms": c.value}
-
-    def close(self):
-        if self.ctx:
-            self.lib.apd_prep_destroy(self.ctx)
-            self.ctx = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 def seg_threshold_q8(threshold: float) -> int:
     """A threshold in grey levels -> include/apd_seg.h's units of 1/256 level."""
@@ -1426,22 +1394,12 @@ def seg_label_mask_host(mask, lib: Optional[C.CDLL] = None) -> np.ndarray:
     return roots
 
 
-class SegEngine:
+class SegEngine(_Context):
     """One apd_seg_ctx (include/apd_seg.h): flat-zone sa_masks on the device. Images and masks are numpy
     arrays or torch tensors; a CUDA tensor is read in place and answered with CUDA tensors."""
 
-    def __init__(self, device: int = 0, lib: Optional[C.CDLL] = None):
-        self.lib = lib or load_library()
-        self.device = device
-        self.shape = None  # (H, W) of the last call
-        self.ctx = self.lib.apd_seg_create(device)
-        if not self.ctx:
-            raise ApdError("apd_seg_create failed: " + (self.lib.apd_seg_last_error(None) or b"?").decode())
-
-    def _check(self, st: int, what: str):
-        if st != 0:
-            msg = (self.lib.apd_seg_last_error(self.ctx) or b"").decode()
-            raise ApdError(f"{what} -> {STATUS.get(st, st)}: {msg}")
+    PREFIX = "apd_seg"
+    shape = None  # (H, W) of the last call
 
     @staticmethod
     def _empty(like, shape, dtype):
@@ -1493,18 +1451,6 @@ class SegEngine:
         ms = (C.c_double * len(SEG_TIMES))()
         self._check(self.lib.apd_seg_get_timing(self.ctx, ms), "apd_seg_get_timing")
         return dict(zip(SEG_TIMES, [float(v) for v in ms]))
-
-    def close(self):
-        if self.ctx:
-            self.lib.apd_seg_destroy(self.ctx)
-            self.ctx = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 def prep_rotation(qvec) -> np.ndarray:
     """(n, 4) quaternions (w, x, y, z), not normalised -> (n, 3, 3) R by include/apd_prep.h's formula."""
@@ -1807,19 +1753,10 @@ def cloud_metrics_dtu(rec_xyz, gt_xyz, mask, bb, res: float, plane, density: flo
     return out
 
 
-class Engine:
+class Engine(_Context):
     """One apd_ctx on one HIP device."""
 
-    def __init__(self, device: int = 0, lib: Optional[C.CDLL] = None):
-        self.lib = lib or load_library()
-        self.ctx = self.lib.apd_create(device)
-        if not self.ctx:
-            raise ApdError("apd_create failed: " + (self.lib.apd_last_error(None) or b"?").decode())
-
-    def _check(self, st: int, what: str):
-        if st != 0:
-            msg = (self.lib.apd_last_error(self.ctx) or b"").decode()
-            raise ApdError(f"{what} -> {STATUS.get(st, st)}: {msg}")
+    PREFIX = "apd"
 
     def set_problem(self, arrays: ProblemArrays):
         pb = arrays.build()
@@ -1922,16 +1859,11 @@ class Engine:
         self._check(self.lib.apd_profile_evaluations(self.ctx, C.byref(n)), "apd_profile_evaluations")
         return n.value
 
-    def close(self):
-        if self.ctx:
-            self.lib.apd_destroy(self.ctx)
-            self.ctx = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    def device_bytes(self) -> int:
+        """Bytes of device memory the context's buffers hold."""
+        n = C.c_size_t()
+        self._check(self.lib.apd_device_bytes(self.ctx, C.byref(n)), "apd_device_bytes")
+        return n.value
 
 
 def scene_problem(scene, ref: int = 0, srcs: Optional[Sequence[int]] = None, params: Optional[ApdParams] = None,

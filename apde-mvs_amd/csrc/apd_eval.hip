@@ -36,6 +36,7 @@
 
 #include "../../include/apd_eval.h"
 #include "apd_dtu.h"
+#include "apd_host.h"
 #include "apd_register.h"
 
 namespace {
@@ -944,80 +945,49 @@ __global__ void __launch_bounds__(64) k_stats_fold(const double *__restrict__ pa
     out[0] = s;
 }
 
-struct Buf {
-    void *p = nullptr;
-    size_t bytes = 0;
-};
-
 inline int grid_for(int64_t n) { return (int)((n + BLOCK - 1) / BLOCK); }
 inline int grid_capped(int64_t n) { return (int)std::min<int64_t>((n + BLOCK - 1) / BLOCK, 4096); }
 
 }  // namespace
 
-struct apd_eval_ctx {
-    int device = 0;
-    hipStream_t stream = nullptr;
+struct apd_eval_ctx : DevCtx {
+    apd_eval_ctx() : DevCtx("apd_eval") {}
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    std::string err;
     // target
-    Buf t_xyz, t_keys, t_keys_s, t_idx, t_idx_s, t_pts, t_boxes;
+    DevBuf t_xyz, t_keys, t_keys_s, t_idx, t_idx_s, t_pts, t_boxes;
     // query / voxel working set
-    Buf q_xyz, q_keys, q_keys_s, q_idx, q_idx_s, q_dist, q_aux;
-    Buf sort_tmp, small;  // small: bounds (6 u32) at 0, counters (u64) from byte 64
+    DevBuf q_xyz, q_keys, q_keys_s, q_idx, q_idx_s, q_dist, q_aux;
+    DevBuf sort_tmp, small;  // small: bounds (6 u32) at 0, counters (u64) from byte 64
     Tree tree{};
     bool has_target = false;
     double build_ms = 0.0, query_ms = 0.0, voxel_ms = 0.0;
     // render / visibility: the key plane of one view, staging for its outputs (render) or for the
     // depth maps of one chunk of views (visibility), and the cloud's own bounds for the Morton order
-    Buf r_keys, r_depth, r_index, r_small;
+    DevBuf r_keys, r_depth, r_index, r_small;
     bool render_morton = false;  // APD_EVAL_RENDER_ORDER=input|morton (input measured faster)
     double render_ms = 0.0, visibility_ms = 0.0;
     // free gap / voxel scores: device copies of dist and gap, the per-run scan of one tolerance and
     // the four sums of every tolerance
-    Buf s_dist, s_gap, s_cnt, s_out;
+    DevBuf s_dist, s_gap, s_cnt, s_out;
     double free_gap_ms = 0.0, scores_ms = 0.0;
     // crop / nearest with index / transform / registration: the polygon, the transformed cloud, the
     // per-block sums and the 19 folded sums; a third event splits the evaluation from the fold
-    Buf c_poly, x_out, g_part, g_sums, n_idx;
+    DevBuf c_poly, x_out, g_part, g_sums, n_idx;
     hipEvent_t ev2 = nullptr;
     double reg_eval_ms = 0.0, reg_fold_ms = 0.0, reg_solve_ms = 0.0, crop_ms = 0.0, transform_ms = 0.0;
     int reg_evaluations = 0;
     // radius thinning: the points in cell order with their ranks, the 9 neighbour runs of every point,
     // a byte of state each, the two worklists, the uploaded ranks and the per-round counters
-    Buf th_pts, th_runs, th_state, th_list0, th_list1, th_rank, th_small;
+    DevBuf th_pts, th_runs, th_state, th_list0, th_list1, th_rank, th_small;
     double thin_sort_ms = 0.0, thin_rounds_ms = 0.0;
     int thin_rounds = 0;
     // observability mask (kept while the caller gives the same pointer and dims), the flags of a call,
     // the statistics' block sums and results
-    Buf m_mask, d_flag, st_part, st_out;
+    DevBuf m_mask, d_flag, st_part, st_out;
     const void *mask_src = nullptr;
     int32_t mask_dims[3] = {0, 0, 0};
     double mask_ms = 0.0, half_space_ms = 0.0, stats_ms = 0.0;
 };
-
-#define EV_OK(ctx, call)                                                                           \
-    do {                                                                                           \
-        hipError_t e_ = (call);                                                                    \
-        if (e_ != hipSuccess) {                                                                    \
-            (ctx)->err = std::string(#call) + ": " + hipGetErrorString(e_);                        \
-            return APD_EDEVICE;                                                                    \
-        }                                                                                          \
-    } while (0)
-
-static int grow(apd_eval_ctx *ctx, Buf &b, size_t bytes) {
-    if (b.bytes >= bytes && b.p) return APD_OK;
-    if (b.p) (void)hipFree(b.p);
-    b.p = nullptr;
-    b.bytes = 0;
-    if (bytes == 0) bytes = 16;
-    if (hipMalloc(&b.p, bytes) != hipSuccess) {
-        b.p = nullptr;
-        ctx->err = "apd_eval: device allocation of " + std::to_string(bytes) + " bytes failed";
-        return APD_ENOMEM;
-    }
-    b.bytes = bytes;
-    return APD_OK;
-}
 
 static int check_n(apd_eval_ctx *ctx, const char *what, int64_t n, const void *p) {
     if (n < 0 || n > (int64_t)INT32_MAX) {
@@ -1032,21 +1002,14 @@ static int check_n(apd_eval_ctx *ctx, const char *what, int64_t n, const void *p
 }
 
 // keys/idx -> keys_s/idx_s, stable, all 64 bits
-static int sort_pairs(apd_eval_ctx *ctx, Buf &keys, Buf &keys_s, Buf &idx, Buf &idx_s, int n) {
+static int sort_pairs(apd_eval_ctx *ctx, DevBuf &keys, DevBuf &keys_s, DevBuf &idx, DevBuf &idx_s, int n) {
     size_t tb = 0;
-    EV_OK(ctx, rocprim::radix_sort_pairs(nullptr, tb, (uint64_t *)keys.p, (uint64_t *)keys_s.p, (int *)idx.p,
+    HIP_OK(ctx, rocprim::radix_sort_pairs(nullptr, tb, (uint64_t *)keys.p, (uint64_t *)keys_s.p, (int *)idx.p,
                                          (int *)idx_s.p, (size_t)n, 0, 64, ctx->stream));
     int st = grow(ctx, ctx->sort_tmp, tb);
     if (st) return st;
-    EV_OK(ctx, rocprim::radix_sort_pairs(ctx->sort_tmp.p, tb, (uint64_t *)keys.p, (uint64_t *)keys_s.p, (int *)idx.p,
+    HIP_OK(ctx, rocprim::radix_sort_pairs(ctx->sort_tmp.p, tb, (uint64_t *)keys.p, (uint64_t *)keys_s.p, (int *)idx.p,
                                          (int *)idx_s.p, (size_t)n, 0, 64, ctx->stream));
-    return APD_OK;
-}
-
-static int elapsed(apd_eval_ctx *ctx, double &ms) {
-    float f = 0.0f;
-    EV_OK(ctx, hipEventElapsedTime(&f, ctx->ev0, ctx->ev1));
-    ms = (double)f;
     return APD_OK;
 }
 
@@ -1071,14 +1034,14 @@ static float d2_bound(float md) {
 static int voxel_sorted_keys(apd_eval_ctx *ctx, const char *what, int n, float voxel, uint32_t *bounds, bool &none) {
     hipStream_t s = ctx->stream;
     int st;
-    EV_OK(ctx, hipMemsetAsync(bounds, 0xFF, 12, s));
-    EV_OK(ctx, hipMemsetAsync(bounds + 3, 0, 12, s));
+    HIP_OK(ctx, hipMemsetAsync(bounds, 0xFF, 12, s));
+    HIP_OK(ctx, hipMemsetAsync(bounds + 3, 0, 12, s));
     hipLaunchKernelGGL(k_voxel_bounds, dim3(grid_capped(n)), dim3(BLOCK), 0, s, (const float *)ctx->q_xyz.p, n, voxel,
                        bounds);
-    EV_OK(ctx, hipGetLastError());
+    HIP_OK(ctx, hipGetLastError());
     uint32_t hb[6];
-    EV_OK(ctx, hipMemcpyAsync(hb, bounds, 24, hipMemcpyDeviceToHost, s));
-    EV_OK(ctx, hipStreamSynchronize(s));
+    HIP_OK(ctx, hipMemcpyAsync(hb, bounds, 24, hipMemcpyDeviceToHost, s));
+    HIP_OK(ctx, hipStreamSynchronize(s));
     none = hb[0] == 0xFFFFFFFFu;
     if (none) return APD_OK;
     float mn[3];
@@ -1098,7 +1061,7 @@ static int voxel_sorted_keys(apd_eval_ctx *ctx, const char *what, int n, float v
     }
     hipLaunchKernelGGL(k_voxel_keys, dim3(grid_for(n)), dim3(BLOCK), 0, s, (const float *)ctx->q_xyz.p, n, voxel,
                        mn[0], mn[1], mn[2], (uint64_t *)ctx->q_keys.p, (int *)ctx->q_idx.p);
-    EV_OK(ctx, hipGetLastError());
+    HIP_OK(ctx, hipGetLastError());
     if ((st = sort_pairs(ctx, ctx->q_keys, ctx->q_keys_s, ctx->q_idx, ctx->q_idx_s, n))) return st;
     return APD_OK;
 }
@@ -1106,14 +1069,10 @@ static int voxel_sorted_keys(apd_eval_ctx *ctx, const char *what, int n, float v
 extern "C" {
 
 apd_eval_ctx *apd_eval_create(int32_t device) {
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || device < 0 || device >= n) return nullptr;
-    if (hipSetDevice(device) != hipSuccess) return nullptr;
-    auto *ctx = new apd_eval_ctx();
-    ctx->device = device;
+    auto *ctx = open_ctx<apd_eval_ctx>(device);
+    if (!ctx) return nullptr;
     if (const char *e = getenv("APD_EVAL_RENDER_ORDER")) ctx->render_morton = strcmp(e, "morton") == 0;
-    if (hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking) != hipSuccess ||
-        hipEventCreate(&ctx->ev0) != hipSuccess || hipEventCreate(&ctx->ev1) != hipSuccess ||
+    if (hipEventCreate(&ctx->ev0) != hipSuccess || hipEventCreate(&ctx->ev1) != hipSuccess ||
         hipEventCreate(&ctx->ev2) != hipSuccess) {
         apd_eval_destroy(ctx);
         return nullptr;
@@ -1124,18 +1083,11 @@ apd_eval_ctx *apd_eval_create(int32_t device) {
 void apd_eval_destroy(apd_eval_ctx *ctx) {
     if (!ctx) return;
     (void)hipSetDevice(ctx->device);
-    for (Buf *b : {&ctx->t_xyz, &ctx->t_keys, &ctx->t_keys_s, &ctx->t_idx, &ctx->t_idx_s, &ctx->t_pts, &ctx->t_boxes,
-                   &ctx->q_xyz, &ctx->q_keys, &ctx->q_keys_s, &ctx->q_idx, &ctx->q_idx_s, &ctx->q_dist, &ctx->q_aux,
-                   &ctx->sort_tmp, &ctx->small, &ctx->r_keys, &ctx->r_depth, &ctx->r_index, &ctx->r_small, &ctx->s_dist,
-                   &ctx->s_gap, &ctx->s_cnt, &ctx->s_out, &ctx->c_poly, &ctx->x_out, &ctx->g_part, &ctx->g_sums,
-                   &ctx->n_idx, &ctx->th_pts, &ctx->th_runs, &ctx->th_state, &ctx->th_list0, &ctx->th_list1,
-                   &ctx->th_rank, &ctx->th_small, &ctx->m_mask, &ctx->d_flag, &ctx->st_part, &ctx->st_out})
-        if (b->p) (void)hipFree(b->p);
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
     if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
     if (ctx->ev2) (void)hipEventDestroy(ctx->ev2);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
-    delete ctx;
+    delete ctx;  // the buffers with it
 }
 
 const char *apd_eval_last_error(const apd_eval_ctx *ctx) {
@@ -1153,28 +1105,28 @@ int32_t apd_eval_set_target(apd_eval_ctx *ctx, int64_t n64, const float *xyz) {
         ctx->has_target = true;
         return APD_OK;
     }
-    EV_OK(ctx, hipSetDevice(ctx->device));
+    HIP_OK(ctx, hipSetDevice(ctx->device));
     ctx->has_target = false;
     if ((st = grow(ctx, ctx->t_xyz, (size_t)n * 12)) || (st = grow(ctx, ctx->t_keys, (size_t)n * 8)) ||
         (st = grow(ctx, ctx->t_keys_s, (size_t)n * 8)) || (st = grow(ctx, ctx->t_idx, (size_t)n * 4)) ||
         (st = grow(ctx, ctx->t_idx_s, (size_t)n * 4)) || (st = grow(ctx, ctx->small, 256)))
         return st;
     hipStream_t s = ctx->stream;
-    EV_OK(ctx, hipMemcpyAsync(ctx->t_xyz.p, xyz, (size_t)n * 12, hipMemcpyDefault, s));
-    EV_OK(ctx, hipEventRecord(ctx->ev0, s));
+    HIP_OK(ctx, hipMemcpyAsync(ctx->t_xyz.p, xyz, (size_t)n * 12, hipMemcpyDefault, s));
+    HIP_OK(ctx, hipEventRecord(ctx->ev0, s));
     uint32_t *bounds = (uint32_t *)ctx->small.p;
     unsigned long long *counter = (unsigned long long *)((char *)ctx->small.p + 64);
-    EV_OK(ctx, hipMemsetAsync(bounds, 0xFF, 12, s));
-    EV_OK(ctx, hipMemsetAsync(bounds + 3, 0, 12, s));
-    EV_OK(ctx, hipMemsetAsync(counter, 0, 8, s));
+    HIP_OK(ctx, hipMemsetAsync(bounds, 0xFF, 12, s));
+    HIP_OK(ctx, hipMemsetAsync(bounds + 3, 0, 12, s));
+    HIP_OK(ctx, hipMemsetAsync(counter, 0, 8, s));
     hipLaunchKernelGGL(k_bounds, dim3(grid_capped(n)), dim3(BLOCK), 0, s, (const float *)ctx->t_xyz.p, n, bounds);
     hipLaunchKernelGGL(k_morton_keys, dim3(grid_for(n)), dim3(BLOCK), 0, s, (const float *)ctx->t_xyz.p, n, bounds,
                        (uint64_t *)ctx->t_keys.p, (int *)ctx->t_idx.p, counter);
-    EV_OK(ctx, hipGetLastError());
+    HIP_OK(ctx, hipGetLastError());
     if ((st = sort_pairs(ctx, ctx->t_keys, ctx->t_keys_s, ctx->t_idx, ctx->t_idx_s, n))) return st;
     unsigned long long nf64 = 0;
-    EV_OK(ctx, hipMemcpyAsync(&nf64, counter, 8, hipMemcpyDeviceToHost, s));
-    EV_OK(ctx, hipStreamSynchronize(s));
+    HIP_OK(ctx, hipMemcpyAsync(&nf64, counter, 8, hipMemcpyDeviceToHost, s));
+    HIP_OK(ctx, hipStreamSynchronize(s));
     const int nf = (int)nf64;
     Tree T{};
     T.nf = nf;
@@ -1199,14 +1151,14 @@ int32_t apd_eval_set_target(apd_eval_ctx *ctx, int64_t n64, const float *xyz) {
             hipLaunchKernelGGL(k_upper_boxes, dim3(grid_for(T.cnt[l])), dim3(BLOCK), 0, s,
                                (const float4 *)(boxes + 2 * (size_t)T.off[l - 1]), T.cnt[l - 1], T.cnt[l],
                                boxes + 2 * (size_t)T.off[l]);
-        EV_OK(ctx, hipGetLastError());
+        HIP_OK(ctx, hipGetLastError());
         T.pts = (const float4 *)ctx->t_pts.p;
         T.boxes = boxes;
         T.keys = (const uint64_t *)ctx->t_keys_s.p;
     }
-    EV_OK(ctx, hipEventRecord(ctx->ev1, s));
-    EV_OK(ctx, hipStreamSynchronize(s));
-    if ((st = elapsed(ctx, ctx->build_ms))) return st;
+    HIP_OK(ctx, hipEventRecord(ctx->ev1, s));
+    HIP_OK(ctx, hipStreamSynchronize(s));
+    if ((st = event_ms(ctx, ctx->ev0, ctx->ev1, ctx->build_ms))) return st;
     ctx->tree = T;
     ctx->has_target = true;
     return APD_OK;
@@ -1229,9 +1181,9 @@ int32_t apd_eval_distances(apd_eval_ctx *ctx, int64_t n64, const float *xyz, flo
         ctx->err = "apd_eval_distances: no target set";
         return APD_ESTATE;
     }
-    EV_OK(ctx, hipSetDevice(ctx->device));
+    HIP_OK(ctx, hipSetDevice(ctx->device));
     std::vector<float> tols((size_t)num_tol);
-    if (num_tol > 0) EV_OK(ctx, hipMemcpy(tols.data(), tol, (size_t)num_tol * 4, hipMemcpyDefault));
+    if (num_tol > 0) HIP_OK(ctx, hipMemcpy(tols.data(), tol, (size_t)num_tol * 4, hipMemcpyDefault));
     for (float t : tols)
         if (!(t >= 0.0f) || t > max_dist) {
             ctx->err = "apd_eval_distances: a tolerance is negative, NaN or above max_dist";
@@ -1242,7 +1194,7 @@ int32_t apd_eval_distances(apd_eval_ctx *ctx, int64_t n64, const float *xyz, flo
     std::vector<unsigned long long> counts((size_t)num_tol, 0ull);
     if (n == 0) {
         if (within && num_tol > 0)
-            EV_OK(ctx, hipMemcpy(within, counts.data(), (size_t)num_tol * 8, hipMemcpyDefault));
+            HIP_OK(ctx, hipMemcpy(within, counts.data(), (size_t)num_tol * 8, hipMemcpyDefault));
         return APD_OK;
     }
     const int ncnt = within ? num_tol : 0;
@@ -1252,21 +1204,21 @@ int32_t apd_eval_distances(apd_eval_ctx *ctx, int64_t n64, const float *xyz, flo
         (st = grow(ctx, ctx->q_aux, (size_t)std::max(ncnt, 1) * 8)) || (st = grow(ctx, ctx->small, 256)))
         return st;
     hipStream_t s = ctx->stream;
-    EV_OK(ctx, hipMemcpyAsync(ctx->q_xyz.p, xyz, (size_t)n * 12, hipMemcpyDefault, s));
-    EV_OK(ctx, hipEventRecord(ctx->ev0, s));
+    HIP_OK(ctx, hipMemcpyAsync(ctx->q_xyz.p, xyz, (size_t)n * 12, hipMemcpyDefault, s));
+    HIP_OK(ctx, hipEventRecord(ctx->ev0, s));
     // queries are keyed over the TARGET's bounding box, still in `small` from set_target (an all-
     // non-finite or empty target leaves no usable box: every key is then 0 or NONE, which is fine)
     const uint32_t *bounds = (const uint32_t *)ctx->small.p;
     hipLaunchKernelGGL(k_morton_keys, dim3(grid_for(n)), dim3(BLOCK), 0, s, (const float *)ctx->q_xyz.p, n, bounds,
                        (uint64_t *)ctx->q_keys.p, (int *)ctx->q_idx.p, (unsigned long long *)nullptr);
-    EV_OK(ctx, hipGetLastError());
+    HIP_OK(ctx, hipGetLastError());
     if ((st = sort_pairs(ctx, ctx->q_keys, ctx->q_keys_s, ctx->q_idx, ctx->q_idx_s, n))) return st;
     hipLaunchKernelGGL(k_nearest, dim3(grid_for(n)), dim3(BLOCK), 0, s, ctx->tree, n,
                        (const uint64_t *)ctx->q_keys_s.p, (const int *)ctx->q_idx_s.p, (const float *)ctx->q_xyz.p,
                        d2_bound(max_dist), max_dist, (float *)ctx->q_dist.p);
-    EV_OK(ctx, hipGetLastError());
+    HIP_OK(ctx, hipGetLastError());
     if (ncnt > 0) {
-        EV_OK(ctx, hipMemsetAsync(ctx->q_aux.p, 0, (size_t)ncnt * 8, s));
+        HIP_OK(ctx, hipMemsetAsync(ctx->q_aux.p, 0, (size_t)ncnt * 8, s));
         for (int k0 = 0; k0 < ncnt; k0 += TOL_CHUNK) {
             TolChunk tc{};
             tc.n = std::min(TOL_CHUNK, ncnt - k0);
@@ -1274,13 +1226,13 @@ int32_t apd_eval_distances(apd_eval_ctx *ctx, int64_t n64, const float *xyz, flo
             hipLaunchKernelGGL(k_count_within, dim3(grid_capped(n)), dim3(BLOCK), 0, s, (const float *)ctx->q_dist.p,
                                n, tc, (unsigned long long *)ctx->q_aux.p + k0);
         }
-        EV_OK(ctx, hipGetLastError());
+        HIP_OK(ctx, hipGetLastError());
     }
-    EV_OK(ctx, hipEventRecord(ctx->ev1, s));
-    if (dist) EV_OK(ctx, hipMemcpyAsync(dist, ctx->q_dist.p, (size_t)n * 4, hipMemcpyDefault, s));
-    if (ncnt > 0) EV_OK(ctx, hipMemcpyAsync(within, ctx->q_aux.p, (size_t)ncnt * 8, hipMemcpyDefault, s));
-    EV_OK(ctx, hipStreamSynchronize(s));
-    return elapsed(ctx, ctx->query_ms);
+    HIP_OK(ctx, hipEventRecord(ctx->ev1, s));
+    if (dist) HIP_OK(ctx, hipMemcpyAsync(dist, ctx->q_dist.p, (size_t)n * 4, hipMemcpyDefault, s));
+    if (ncnt > 0) HIP_OK(ctx, hipMemcpyAsync(within, ctx->q_aux.p, (size_t)ncnt * 8, hipMemcpyDefault, s));
+    HIP_OK(ctx, hipStreamSynchronize(s));
+    return event_ms(ctx, ctx->ev0, ctx->ev1, ctx->query_ms);
 }
 
 int32_t apd_eval_voxel_downsample(apd_eval_ctx *ctx, int64_t n64, const float *xyz, float voxel, int32_t *keep_idx,
@@ -1296,12 +1248,12 @@ int32_t apd_eval_voxel_downsample(apd_eval_ctx *ctx, int64_t n64, const float *x
         ctx->err = "apd_eval_voxel_downsample: NULL output";
         return APD_EINVAL;
     }
-    EV_OK(ctx, hipSetDevice(ctx->device));
+    HIP_OK(ctx, hipSetDevice(ctx->device));
     const int n = (int)n64;
     ctx->voxel_ms = 0.0;
     unsigned long long kept = 0;
     if (n == 0) {
-        EV_OK(ctx, hipMemcpy(n_keep, &kept, 8, hipMemcpyDefault));
+        HIP_OK(ctx, hipMemcpy(n_keep, &kept, 8, hipMemcpyDefault));
         return APD_OK;
     }
     // q_dist holds the head flags, q_aux their exclusive scan, q_keys (reused) the kept indices
@@ -1314,32 +1266,32 @@ int32_t apd_eval_voxel_downsample(apd_eval_ctx *ctx, int64_t n64, const float *x
     uint32_t *bounds = (uint32_t *)ctx->q_aux.p;
     unsigned long long *counter = (unsigned long long *)((char *)ctx->q_aux.p + 64);
     hipStream_t s = ctx->stream;
-    EV_OK(ctx, hipMemcpyAsync(ctx->q_xyz.p, xyz, (size_t)n * 12, hipMemcpyDefault, s));
-    EV_OK(ctx, hipEventRecord(ctx->ev0, s));
+    HIP_OK(ctx, hipMemcpyAsync(ctx->q_xyz.p, xyz, (size_t)n * 12, hipMemcpyDefault, s));
+    HIP_OK(ctx, hipEventRecord(ctx->ev0, s));
     bool none = false;
     if ((st = voxel_sorted_keys(ctx, "apd_eval_voxel_downsample", n, voxel, bounds, none))) return st;
     if (none) {  // no finite point
-        EV_OK(ctx, hipMemcpy(n_keep, &kept, 8, hipMemcpyDefault));
+        HIP_OK(ctx, hipMemcpy(n_keep, &kept, 8, hipMemcpyDefault));
         return APD_OK;
     }
     int *flag = (int *)ctx->q_dist.p, *pos = (int *)ctx->q_aux.p + 32, *keep = (int *)ctx->q_keys.p;
-    EV_OK(ctx, hipMemsetAsync(flag, 0, (size_t)n * 4, s));
+    HIP_OK(ctx, hipMemsetAsync(flag, 0, (size_t)n * 4, s));
     hipLaunchKernelGGL(k_voxel_heads, dim3(grid_for(n)), dim3(BLOCK), 0, s, (const uint64_t *)ctx->q_keys_s.p,
                        (const int *)ctx->q_idx_s.p, n, flag);
-    EV_OK(ctx, hipGetLastError());
+    HIP_OK(ctx, hipGetLastError());
     size_t tb = 0;
-    EV_OK(ctx, rocprim::exclusive_scan(nullptr, tb, flag, pos, 0, (size_t)n, rocprim::plus<int>(), s));
+    HIP_OK(ctx, rocprim::exclusive_scan(nullptr, tb, flag, pos, 0, (size_t)n, rocprim::plus<int>(), s));
     if ((st = grow(ctx, ctx->sort_tmp, tb))) return st;
-    EV_OK(ctx, rocprim::exclusive_scan(ctx->sort_tmp.p, tb, flag, pos, 0, (size_t)n, rocprim::plus<int>(), s));
+    HIP_OK(ctx, rocprim::exclusive_scan(ctx->sort_tmp.p, tb, flag, pos, 0, (size_t)n, rocprim::plus<int>(), s));
     hipLaunchKernelGGL(k_voxel_compact, dim3(grid_for(n)), dim3(BLOCK), 0, s, (const int *)flag, (const int *)pos, n,
                        keep, counter);
-    EV_OK(ctx, hipGetLastError());
-    EV_OK(ctx, hipEventRecord(ctx->ev1, s));
-    EV_OK(ctx, hipMemcpyAsync(&kept, counter, 8, hipMemcpyDeviceToHost, s));
-    EV_OK(ctx, hipStreamSynchronize(s));
-    if (kept > 0) EV_OK(ctx, hipMemcpy(keep_idx, keep, (size_t)kept * 4, hipMemcpyDefault));
-    EV_OK(ctx, hipMemcpy(n_keep, &kept, 8, hipMemcpyDefault));
-    return elapsed(ctx, ctx->voxel_ms);
+    HIP_OK(ctx, hipGetLastError());
+    HIP_OK(ctx, hipEventRecord(ctx->ev1, s));
+    HIP_OK(ctx, hipMemcpyAsync(&kept, counter, 8, hipMemcpyDeviceToHost, s));
+    HIP_OK(ctx, hipStreamSynchronize(s));
+    if (kept > 0) HIP_OK(ctx, hipMemcpy(keep_idx, keep, (size_t)kept * 4, hipMemcpyDefault));
+    HIP_OK(ctx, hipMemcpy(n_keep, &kept, 8, hipMemcpyDefault));
+    return event_ms(ctx, ctx->ev0, ctx->ev1, ctx->voxel_ms);
 }
 
 int32_t apd_eval_get_timing(apd_eval_ctx *ctx, double *build_ms, double *query_ms, double *voxel_ms) {
@@ -1384,7 +1336,7 @@ int32_t apd_eval_render_depth(apd_eval_ctx *ctx, int64_t n64, const float *xyz, 
         }
     ctx->render_ms = 0.0;
     if (num_views == 0) return APD_OK;
-    EV_OK(ctx, hipSetDevice(ctx->device));
+    HIP_OK(ctx, hipSetDevice(ctx->device));
     const int n = (int)n64;
     size_t max_pix = 0;
     bool any_index = false;
@@ -1400,7 +1352,7 @@ int32_t apd_eval_render_depth(apd_eval_ctx *ctx, int64_t n64, const float *xyz, 
     double ms = 0.0, total = 0.0;
     if (n > 0) {
         if ((st = grow(ctx, ctx->q_xyz, (size_t)n * 12))) return st;
-        EV_OK(ctx, hipMemcpyAsync(ctx->q_xyz.p, xyz, (size_t)n * 12, hipMemcpyDefault, s));
+        HIP_OK(ctx, hipMemcpyAsync(ctx->q_xyz.p, xyz, (size_t)n * 12, hipMemcpyDefault, s));
         if (ctx->render_morton) {
             // the key-and-sort path of set_target over the cloud's own box; `small` keeps the target's
             if ((st = grow(ctx, ctx->q_keys, (size_t)n * 8)) || (st = grow(ctx, ctx->q_keys_s, (size_t)n * 8)) ||
@@ -1408,18 +1360,18 @@ int32_t apd_eval_render_depth(apd_eval_ctx *ctx, int64_t n64, const float *xyz, 
                 (st = grow(ctx, ctx->r_small, 64)))
                 return st;
             uint32_t *bounds = (uint32_t *)ctx->r_small.p;
-            EV_OK(ctx, hipEventRecord(ctx->ev0, s));
-            EV_OK(ctx, hipMemsetAsync(bounds, 0xFF, 12, s));
-            EV_OK(ctx, hipMemsetAsync(bounds + 3, 0, 12, s));
+            HIP_OK(ctx, hipEventRecord(ctx->ev0, s));
+            HIP_OK(ctx, hipMemsetAsync(bounds, 0xFF, 12, s));
+            HIP_OK(ctx, hipMemsetAsync(bounds + 3, 0, 12, s));
             hipLaunchKernelGGL(k_bounds, dim3(grid_capped(n)), dim3(BLOCK), 0, s, (const float *)ctx->q_xyz.p, n, bounds);
             hipLaunchKernelGGL(k_morton_keys, dim3(grid_for(n)), dim3(BLOCK), 0, s, (const float *)ctx->q_xyz.p, n,
                                (const uint32_t *)bounds, (uint64_t *)ctx->q_keys.p, (int *)ctx->q_idx.p,
                                (unsigned long long *)nullptr);
-            EV_OK(ctx, hipGetLastError());
+            HIP_OK(ctx, hipGetLastError());
             if ((st = sort_pairs(ctx, ctx->q_keys, ctx->q_keys_s, ctx->q_idx, ctx->q_idx_s, n))) return st;
-            EV_OK(ctx, hipEventRecord(ctx->ev1, s));
-            EV_OK(ctx, hipStreamSynchronize(s));
-            if ((st = elapsed(ctx, ms))) return st;
+            HIP_OK(ctx, hipEventRecord(ctx->ev1, s));
+            HIP_OK(ctx, hipStreamSynchronize(s));
+            if ((st = event_ms(ctx, ctx->ev0, ctx->ev1, ms))) return st;
             total += ms;
             order = (const int *)ctx->q_idx_s.p;
         }
@@ -1427,19 +1379,19 @@ int32_t apd_eval_render_depth(apd_eval_ctx *ctx, int64_t n64, const float *xyz, 
     for (int v = 0; v < num_views; ++v) {
         const int npix = cams[v].width * cams[v].height;
         int *idx_out = (index && index[v]) ? (int *)ctx->r_index.p : nullptr;
-        EV_OK(ctx, hipEventRecord(ctx->ev0, s));
-        EV_OK(ctx, hipMemsetAsync(ctx->r_keys.p, 0xFF, (size_t)npix * 8, s));
+        HIP_OK(ctx, hipEventRecord(ctx->ev0, s));
+        HIP_OK(ctx, hipMemsetAsync(ctx->r_keys.p, 0xFF, (size_t)npix * 8, s));
         if (n > 0)
             hipLaunchKernelGGL(k_splat, dim3(grid_for(n)), dim3(BLOCK), 0, s, (const float *)ctx->q_xyz.p, order, n,
                                cams[v], (int)splat, (uint64_t *)ctx->r_keys.p);
         hipLaunchKernelGGL(k_resolve, dim3(grid_for(npix)), dim3(BLOCK), 0, s, (const uint64_t *)ctx->r_keys.p, npix,
                            (float *)ctx->r_depth.p, idx_out);
-        EV_OK(ctx, hipGetLastError());
-        EV_OK(ctx, hipEventRecord(ctx->ev1, s));
-        EV_OK(ctx, hipMemcpyAsync(depth[v], ctx->r_depth.p, (size_t)npix * 4, hipMemcpyDefault, s));
-        if (idx_out) EV_OK(ctx, hipMemcpyAsync(index[v], idx_out, (size_t)npix * 4, hipMemcpyDefault, s));
-        EV_OK(ctx, hipStreamSynchronize(s));
-        if ((st = elapsed(ctx, ms))) return st;
+        HIP_OK(ctx, hipGetLastError());
+        HIP_OK(ctx, hipEventRecord(ctx->ev1, s));
+        HIP_OK(ctx, hipMemcpyAsync(depth[v], ctx->r_depth.p, (size_t)npix * 4, hipMemcpyDefault, s));
+        if (idx_out) HIP_OK(ctx, hipMemcpyAsync(index[v], idx_out, (size_t)npix * 4, hipMemcpyDefault, s));
+        HIP_OK(ctx, hipStreamSynchronize(s));
+        if ((st = event_ms(ctx, ctx->ev0, ctx->ev1, ms))) return st;
         total += ms;
     }
     ctx->render_ms = total;
@@ -1465,12 +1417,12 @@ int32_t apd_eval_visibility(apd_eval_ctx *ctx, int64_t n64, const float *xyz, in
             ctx->err = "apd_eval_visibility: NULL depth map";
             return APD_EINVAL;
         }
-    EV_OK(ctx, hipSetDevice(ctx->device));
+    HIP_OK(ctx, hipSetDevice(ctx->device));
     const int n = (int)n64;
     ctx->visibility_ms = 0.0;
     unsigned long long any = 0;
     if (n == 0) {
-        if (n_visible_any) EV_OK(ctx, hipMemcpy(n_visible_any, &any, 8, hipMemcpyDefault));
+        if (n_visible_any) HIP_OK(ctx, hipMemcpy(n_visible_any, &any, 8, hipMemcpyDefault));
         return APD_OK;
     }
     if ((st = grow(ctx, ctx->q_xyz, (size_t)n * 12)) || (st = grow(ctx, ctx->q_dist, (size_t)n * 4)) ||
@@ -1479,9 +1431,9 @@ int32_t apd_eval_visibility(apd_eval_ctx *ctx, int64_t n64, const float *xyz, in
     hipStream_t s = ctx->stream;
     int *d_seen = (int *)ctx->q_dist.p;
     unsigned long long *counter = (unsigned long long *)((char *)ctx->r_small.p + 32);
-    EV_OK(ctx, hipMemcpyAsync(ctx->q_xyz.p, xyz, (size_t)n * 12, hipMemcpyDefault, s));
-    EV_OK(ctx, hipMemsetAsync(counter, 0, 8, s));
-    if (num_views == 0) EV_OK(ctx, hipMemsetAsync(d_seen, 0, (size_t)n * 4, s));
+    HIP_OK(ctx, hipMemcpyAsync(ctx->q_xyz.p, xyz, (size_t)n * 12, hipMemcpyDefault, s));
+    HIP_OK(ctx, hipMemsetAsync(counter, 0, 8, s));
+    if (num_views == 0) HIP_OK(ctx, hipMemsetAsync(d_seen, 0, (size_t)n * 4, s));
     const float factor = 1.0f + rel_tol;  // one fp32 addition, made once
     double ms = 0.0, total = 0.0;
     for (int v0 = 0; v0 < num_views; v0 += VIS_CHUNK) {
@@ -1495,23 +1447,23 @@ int32_t apd_eval_visibility(apd_eval_ctx *ctx, int64_t n64, const float *xyz, in
             const size_t b = (size_t)cams[v0 + k].width * (size_t)cams[v0 + k].height * 4;
             vv.cam[k] = cams[v0 + k];
             vv.depth[k] = (const float *)((char *)ctx->r_depth.p + off);
-            EV_OK(ctx, hipMemcpyAsync((char *)ctx->r_depth.p + off, depth[v0 + k], b, hipMemcpyDefault, s));
+            HIP_OK(ctx, hipMemcpyAsync((char *)ctx->r_depth.p + off, depth[v0 + k], b, hipMemcpyDefault, s));
             off += b;
         }
         const bool last = v0 + VIS_CHUNK >= num_views;
-        EV_OK(ctx, hipEventRecord(ctx->ev0, s));
+        HIP_OK(ctx, hipEventRecord(ctx->ev0, s));
         hipLaunchKernelGGL(k_visibility, dim3(grid_for(n)), dim3(BLOCK), 0, s, (const float *)ctx->q_xyz.p, n, vv, factor,
                            v0 == 0 ? 1 : 0, d_seen, last ? counter : (unsigned long long *)nullptr);
-        EV_OK(ctx, hipGetLastError());
-        EV_OK(ctx, hipEventRecord(ctx->ev1, s));
-        EV_OK(ctx, hipStreamSynchronize(s));  // the next chunk reuses the staging buffer and the events
-        if ((st = elapsed(ctx, ms))) return st;
+        HIP_OK(ctx, hipGetLastError());
+        HIP_OK(ctx, hipEventRecord(ctx->ev1, s));
+        HIP_OK(ctx, hipStreamSynchronize(s));  // the next chunk reuses the staging buffer and the events
+        if ((st = event_ms(ctx, ctx->ev0, ctx->ev1, ms))) return st;
         total += ms;
     }
-    EV_OK(ctx, hipMemcpyAsync(seen, d_seen, (size_t)n * 4, hipMemcpyDefault, s));
-    EV_OK(ctx, hipMemcpyAsync(&any, counter, 8, hipMemcpyDeviceToHost, s));
-    EV_OK(ctx, hipStreamSynchronize(s));
-    if (n_visible_any) EV_OK(ctx, hipMemcpy(n_visible_any, &any, 8, hipMemcpyDefault));
+    HIP_OK(ctx, hipMemcpyAsync(seen, d_seen, (size_t)n * 4, hipMemcpyDefault, s));
+    HIP_OK(ctx, hipMemcpyAsync(&any, counter, 8, hipMemcpyDeviceToHost, s));
+    HIP_OK(ctx, hipStreamSynchronize(s));
+    if (n_visible_any) HIP_OK(ctx, hipMemcpy(n_visible_any, &any, 8, hipMemcpyDefault));
     ctx->visibility_ms = total;
     return APD_OK;
 }
@@ -1562,11 +1514,11 @@ int32_t apd_eval_free_gap(apd_eval_ctx *ctx, int64_t n64, const float *xyz, int3
     ctx->free_gap_ms = 0.0;
     const int n = (int)n64;
     if (n == 0) return APD_OK;
-    EV_OK(ctx, hipSetDevice(ctx->device));
+    HIP_OK(ctx, hipSetDevice(ctx->device));
     if ((st = grow(ctx, ctx->q_xyz, (size_t)n * 12)) || (st = grow(ctx, ctx->q_dist, (size_t)n * 4))) return st;
     hipStream_t s = ctx->stream;
     float *d_gap = (float *)ctx->q_dist.p;
-    EV_OK(ctx, hipMemcpyAsync(ctx->q_xyz.p, xyz, (size_t)n * 12, hipMemcpyDefault, s));
+    HIP_OK(ctx, hipMemcpyAsync(ctx->q_xyz.p, xyz, (size_t)n * 12, hipMemcpyDefault, s));
     double ms = 0.0, total = 0.0;
     int v0 = 0;
     do {  // at least once: without views the kernel still writes -inf
@@ -1580,21 +1532,21 @@ int32_t apd_eval_free_gap(apd_eval_ctx *ctx, int64_t n64, const float *xyz, int3
             const size_t b = (size_t)cams[v0 + k].width * (size_t)cams[v0 + k].height * 4;
             vv.cam[k] = cams[v0 + k];
             vv.depth[k] = (const float *)((char *)ctx->r_depth.p + off);
-            EV_OK(ctx, hipMemcpyAsync((char *)ctx->r_depth.p + off, depth[v0 + k], b, hipMemcpyDefault, s));
+            HIP_OK(ctx, hipMemcpyAsync((char *)ctx->r_depth.p + off, depth[v0 + k], b, hipMemcpyDefault, s));
             off += b;
         }
-        EV_OK(ctx, hipEventRecord(ctx->ev0, s));
+        HIP_OK(ctx, hipEventRecord(ctx->ev0, s));
         hipLaunchKernelGGL(k_free_gap, dim3(grid_for(n)), dim3(BLOCK), 0, s, (const float *)ctx->q_xyz.p, n, vv,
                            v0 == 0 ? 1 : 0, d_gap);
-        EV_OK(ctx, hipGetLastError());
-        EV_OK(ctx, hipEventRecord(ctx->ev1, s));
-        EV_OK(ctx, hipStreamSynchronize(s));  // the next chunk reuses the staging buffer and the events
-        if ((st = elapsed(ctx, ms))) return st;
+        HIP_OK(ctx, hipGetLastError());
+        HIP_OK(ctx, hipEventRecord(ctx->ev1, s));
+        HIP_OK(ctx, hipStreamSynchronize(s));  // the next chunk reuses the staging buffer and the events
+        if ((st = event_ms(ctx, ctx->ev0, ctx->ev1, ms))) return st;
         total += ms;
         v0 += VIS_CHUNK;
     } while (v0 < num_views);
-    EV_OK(ctx, hipMemcpyAsync(gap, d_gap, (size_t)n * 4, hipMemcpyDefault, s));
-    EV_OK(ctx, hipStreamSynchronize(s));
+    HIP_OK(ctx, hipMemcpyAsync(gap, d_gap, (size_t)n * 4, hipMemcpyDefault, s));
+    HIP_OK(ctx, hipStreamSynchronize(s));
     ctx->free_gap_ms = total;
     return APD_OK;
 }
@@ -1621,9 +1573,9 @@ int32_t apd_eval_voxel_scores(apd_eval_ctx *ctx, int64_t n64, const float *xyz, 
         ctx->err = "apd_eval_voxel_scores: NULL output";
         return APD_EINVAL;
     }
-    EV_OK(ctx, hipSetDevice(ctx->device));
+    HIP_OK(ctx, hipSetDevice(ctx->device));
     std::vector<float> tols((size_t)num_tol);
-    if (num_tol > 0) EV_OK(ctx, hipMemcpy(tols.data(), tol, (size_t)num_tol * 4, hipMemcpyDefault));
+    if (num_tol > 0) HIP_OK(ctx, hipMemcpy(tols.data(), tol, (size_t)num_tol * 4, hipMemcpyDefault));
     for (float t : tols)
         if (!(t >= 0.0f)) {
             ctx->err = "apd_eval_voxel_scores: a tolerance is negative or NaN";
@@ -1638,7 +1590,7 @@ int32_t apd_eval_voxel_scores(apd_eval_ctx *ctx, int64_t n64, const float *xyz, 
         void *const outs[4] = {good, bad, ratio_sum, voxels};
         for (int q = 0; q < 4 && num_tol > 0; ++q) {
             for (int k = 0; k < num_tol; ++k) col[(size_t)k] = sums[(size_t)k * 4 + q];
-            EV_OK(ctx, hipMemcpy(outs[q], col.data(), (size_t)num_tol * 8, hipMemcpyDefault));
+            HIP_OK(ctx, hipMemcpy(outs[q], col.data(), (size_t)num_tol * 8, hipMemcpyDefault));
         }
         return APD_OK;
     };
@@ -1650,10 +1602,10 @@ int32_t apd_eval_voxel_scores(apd_eval_ctx *ctx, int64_t n64, const float *xyz, 
         (st = grow(ctx, ctx->s_cnt, (size_t)n * 8)) || (st = grow(ctx, ctx->s_out, (size_t)std::max(num_tol, 1) * 32)))
         return st;
     hipStream_t s = ctx->stream;
-    EV_OK(ctx, hipMemcpyAsync(ctx->q_xyz.p, xyz, (size_t)n * 12, hipMemcpyDefault, s));
-    EV_OK(ctx, hipMemcpyAsync(ctx->s_dist.p, dist, (size_t)n * 4, hipMemcpyDefault, s));
-    if (gap) EV_OK(ctx, hipMemcpyAsync(ctx->s_gap.p, gap, (size_t)n * 4, hipMemcpyDefault, s));
-    EV_OK(ctx, hipEventRecord(ctx->ev0, s));
+    HIP_OK(ctx, hipMemcpyAsync(ctx->q_xyz.p, xyz, (size_t)n * 12, hipMemcpyDefault, s));
+    HIP_OK(ctx, hipMemcpyAsync(ctx->s_dist.p, dist, (size_t)n * 4, hipMemcpyDefault, s));
+    if (gap) HIP_OK(ctx, hipMemcpyAsync(ctx->s_gap.p, gap, (size_t)n * 4, hipMemcpyDefault, s));
+    HIP_OK(ctx, hipEventRecord(ctx->ev0, s));
     bool none = false;
     // its own scratch for the bounds, as voxel_downsample: `small` keeps the target's box
     if ((st = voxel_sorted_keys(ctx, "apd_eval_voxel_scores", n, voxel, (uint32_t *)ctx->q_aux.p, none))) return st;
@@ -1661,28 +1613,28 @@ int32_t apd_eval_voxel_scores(apd_eval_ctx *ctx, int64_t n64, const float *xyz, 
     const uint64_t *keys = (const uint64_t *)ctx->q_keys_s.p;
     uint64_t *cnt = (uint64_t *)ctx->s_cnt.p;
     unsigned long long *out = (unsigned long long *)ctx->s_out.p;
-    EV_OK(ctx, hipMemsetAsync(out, 0, (size_t)num_tol * 32, s));
+    HIP_OK(ctx, hipMemsetAsync(out, 0, (size_t)num_tol * 32, s));
     // one tolerance at a time: the scratch is one uint64 per point whatever num_tol is
     for (int k = 0; k < num_tol; ++k) {
         const ClassOf cls{(const int *)ctx->q_idx_s.p, (const float *)ctx->s_dist.p,
                           gap ? (const float *)ctx->s_gap.p : nullptr, tols[(size_t)k]};
         auto vals = rocprim::make_transform_iterator(rocprim::counting_iterator<int>(0), cls);
         size_t tb = 0;
-        EV_OK(ctx, rocprim::inclusive_scan_by_key(nullptr, tb, keys, vals, cnt, (size_t)n, rocprim::plus<uint64_t>(),
+        HIP_OK(ctx, rocprim::inclusive_scan_by_key(nullptr, tb, keys, vals, cnt, (size_t)n, rocprim::plus<uint64_t>(),
                                                   rocprim::equal_to<uint64_t>(), s));
         if ((st = grow(ctx, ctx->sort_tmp, tb))) return st;
-        EV_OK(ctx, rocprim::inclusive_scan_by_key(ctx->sort_tmp.p, tb, keys, vals, cnt, (size_t)n,
+        HIP_OK(ctx, rocprim::inclusive_scan_by_key(ctx->sort_tmp.p, tb, keys, vals, cnt, (size_t)n,
                                                   rocprim::plus<uint64_t>(), rocprim::equal_to<uint64_t>(), s));
         hipLaunchKernelGGL(k_voxel_ratio, dim3(std::min(grid_for(n), RATIO_GRID)), dim3(BLOCK), 0, s, keys,
                            (const uint64_t *)cnt, n,
                            out + 4 * (size_t)k);
-        EV_OK(ctx, hipGetLastError());
+        HIP_OK(ctx, hipGetLastError());
     }
-    EV_OK(ctx, hipEventRecord(ctx->ev1, s));
-    EV_OK(ctx, hipMemcpyAsync(sums.data(), out, (size_t)num_tol * 32, hipMemcpyDeviceToHost, s));
-    EV_OK(ctx, hipStreamSynchronize(s));
+    HIP_OK(ctx, hipEventRecord(ctx->ev1, s));
+    HIP_OK(ctx, hipMemcpyAsync(sums.data(), out, (size_t)num_tol * 32, hipMemcpyDeviceToHost, s));
+    HIP_OK(ctx, hipStreamSynchronize(s));
     if ((st = deliver())) return st;
-    return elapsed(ctx, ctx->scores_ms);
+    return event_ms(ctx, ctx->ev0, ctx->ev1, ctx->scores_ms);
 }
 
 int32_t apd_eval_get_protocol_timing(apd_eval_ctx *ctx, double *free_gap_ms, double *scores_ms) {
@@ -1728,12 +1680,12 @@ int32_t apd_eval_crop_volume(apd_eval_ctx *ctx, int64_t n64, const float *xyz, c
             ctx->err = "apd_eval_crop_volume: a non-finite polygon vertex";
             return APD_EINVAL;
         }
-    EV_OK(ctx, hipSetDevice(ctx->device));
+    HIP_OK(ctx, hipSetDevice(ctx->device));
     const int n = (int)n64;
     ctx->crop_ms = 0.0;
     unsigned long long kept = 0;
     if (n == 0) {
-        EV_OK(ctx, hipMemcpy(n_keep, &kept, 8, hipMemcpyDefault));
+        HIP_OK(ctx, hipMemcpy(n_keep, &kept, 8, hipMemcpyDefault));
         return APD_OK;
     }
     // q_dist holds the flags, q_aux their exclusive scan from byte 128 and the kept count at byte 64,
@@ -1745,25 +1697,25 @@ int32_t apd_eval_crop_volume(apd_eval_ctx *ctx, int64_t n64, const float *xyz, c
     unsigned long long *counter = (unsigned long long *)((char *)ctx->q_aux.p + 64);
     int *flag = (int *)ctx->q_dist.p, *pos = (int *)ctx->q_aux.p + 32, *keep = (int *)ctx->q_keys.p;
     hipStream_t s = ctx->stream;
-    EV_OK(ctx, hipMemcpyAsync(ctx->q_xyz.p, xyz, (size_t)n * 12, hipMemcpyDefault, s));
-    EV_OK(ctx, hipMemcpyAsync(ctx->c_poly.p, poly, (size_t)m * 16, hipMemcpyHostToDevice, s));
-    EV_OK(ctx, hipEventRecord(ctx->ev0, s));
+    HIP_OK(ctx, hipMemcpyAsync(ctx->q_xyz.p, xyz, (size_t)n * 12, hipMemcpyDefault, s));
+    HIP_OK(ctx, hipMemcpyAsync(ctx->c_poly.p, poly, (size_t)m * 16, hipMemcpyHostToDevice, s));
+    HIP_OK(ctx, hipEventRecord(ctx->ev0, s));
     hipLaunchKernelGGL(k_crop_flags, dim3(grid_for(n)), dim3(BLOCK), 0, s, (const float *)ctx->q_xyz.p, n, rows_of(T),
                        T ? 1 : 0, (int)axis, axis_min, axis_max, (int)m, (const double *)ctx->c_poly.p, flag);
-    EV_OK(ctx, hipGetLastError());
+    HIP_OK(ctx, hipGetLastError());
     size_t tb = 0;
-    EV_OK(ctx, rocprim::exclusive_scan(nullptr, tb, flag, pos, 0, (size_t)n, rocprim::plus<int>(), s));
+    HIP_OK(ctx, rocprim::exclusive_scan(nullptr, tb, flag, pos, 0, (size_t)n, rocprim::plus<int>(), s));
     if ((st = grow(ctx, ctx->sort_tmp, tb))) return st;
-    EV_OK(ctx, rocprim::exclusive_scan(ctx->sort_tmp.p, tb, flag, pos, 0, (size_t)n, rocprim::plus<int>(), s));
+    HIP_OK(ctx, rocprim::exclusive_scan(ctx->sort_tmp.p, tb, flag, pos, 0, (size_t)n, rocprim::plus<int>(), s));
     hipLaunchKernelGGL(k_voxel_compact, dim3(grid_for(n)), dim3(BLOCK), 0, s, (const int *)flag, (const int *)pos, n,
                        keep, counter);
-    EV_OK(ctx, hipGetLastError());
-    EV_OK(ctx, hipEventRecord(ctx->ev1, s));
-    EV_OK(ctx, hipMemcpyAsync(&kept, counter, 8, hipMemcpyDeviceToHost, s));
-    EV_OK(ctx, hipStreamSynchronize(s));  // the polygon has been read: the caller's array is free again
-    if (kept > 0) EV_OK(ctx, hipMemcpy(keep_idx, keep, (size_t)kept * 4, hipMemcpyDefault));
-    EV_OK(ctx, hipMemcpy(n_keep, &kept, 8, hipMemcpyDefault));
-    return elapsed(ctx, ctx->crop_ms);
+    HIP_OK(ctx, hipGetLastError());
+    HIP_OK(ctx, hipEventRecord(ctx->ev1, s));
+    HIP_OK(ctx, hipMemcpyAsync(&kept, counter, 8, hipMemcpyDeviceToHost, s));
+    HIP_OK(ctx, hipStreamSynchronize(s));  // the polygon has been read: the caller's array is free again
+    if (kept > 0) HIP_OK(ctx, hipMemcpy(keep_idx, keep, (size_t)kept * 4, hipMemcpyDefault));
+    HIP_OK(ctx, hipMemcpy(n_keep, &kept, 8, hipMemcpyDefault));
+    return event_ms(ctx, ctx->ev0, ctx->ev1, ctx->crop_ms);
 }
 
 int32_t apd_eval_nearest(apd_eval_ctx *ctx, int64_t n64, const float *xyz, float max_dist, float *dist, int32_t *idx) {
@@ -1781,29 +1733,29 @@ int32_t apd_eval_nearest(apd_eval_ctx *ctx, int64_t n64, const float *xyz, float
     const int n = (int)n64;
     ctx->query_ms = 0.0;
     if (n == 0) return APD_OK;
-    EV_OK(ctx, hipSetDevice(ctx->device));
+    HIP_OK(ctx, hipSetDevice(ctx->device));
     if ((st = grow(ctx, ctx->q_xyz, (size_t)n * 12)) || (st = grow(ctx, ctx->q_keys, (size_t)n * 8)) ||
         (st = grow(ctx, ctx->q_keys_s, (size_t)n * 8)) || (st = grow(ctx, ctx->q_idx, (size_t)n * 4)) ||
         (st = grow(ctx, ctx->q_idx_s, (size_t)n * 4)) || (st = grow(ctx, ctx->q_dist, (size_t)n * 4)) ||
         (st = grow(ctx, ctx->n_idx, (size_t)n * 4)) || (st = grow(ctx, ctx->small, 256)))
         return st;
     hipStream_t s = ctx->stream;
-    EV_OK(ctx, hipMemcpyAsync(ctx->q_xyz.p, xyz, (size_t)n * 12, hipMemcpyDefault, s));
-    EV_OK(ctx, hipEventRecord(ctx->ev0, s));
+    HIP_OK(ctx, hipMemcpyAsync(ctx->q_xyz.p, xyz, (size_t)n * 12, hipMemcpyDefault, s));
+    HIP_OK(ctx, hipEventRecord(ctx->ev0, s));
     const uint32_t *bounds = (const uint32_t *)ctx->small.p;  // the target's box, as in apd_eval_distances
     hipLaunchKernelGGL(k_morton_keys, dim3(grid_for(n)), dim3(BLOCK), 0, s, (const float *)ctx->q_xyz.p, n, bounds,
                        (uint64_t *)ctx->q_keys.p, (int *)ctx->q_idx.p, (unsigned long long *)nullptr);
-    EV_OK(ctx, hipGetLastError());
+    HIP_OK(ctx, hipGetLastError());
     if ((st = sort_pairs(ctx, ctx->q_keys, ctx->q_keys_s, ctx->q_idx, ctx->q_idx_s, n))) return st;
     hipLaunchKernelGGL(k_nearest_idx, dim3(grid_for(n)), dim3(BLOCK), 0, s, ctx->tree, (const int *)ctx->t_idx_s.p, n,
                        (const uint64_t *)ctx->q_keys_s.p, (const int *)ctx->q_idx_s.p, (const float *)ctx->q_xyz.p,
                        d2_bound(max_dist), max_dist, (float *)ctx->q_dist.p, (int *)ctx->n_idx.p);
-    EV_OK(ctx, hipGetLastError());
-    EV_OK(ctx, hipEventRecord(ctx->ev1, s));
-    if (dist) EV_OK(ctx, hipMemcpyAsync(dist, ctx->q_dist.p, (size_t)n * 4, hipMemcpyDefault, s));
-    if (idx) EV_OK(ctx, hipMemcpyAsync(idx, ctx->n_idx.p, (size_t)n * 4, hipMemcpyDefault, s));
-    EV_OK(ctx, hipStreamSynchronize(s));
-    return elapsed(ctx, ctx->query_ms);
+    HIP_OK(ctx, hipGetLastError());
+    HIP_OK(ctx, hipEventRecord(ctx->ev1, s));
+    if (dist) HIP_OK(ctx, hipMemcpyAsync(dist, ctx->q_dist.p, (size_t)n * 4, hipMemcpyDefault, s));
+    if (idx) HIP_OK(ctx, hipMemcpyAsync(idx, ctx->n_idx.p, (size_t)n * 4, hipMemcpyDefault, s));
+    HIP_OK(ctx, hipStreamSynchronize(s));
+    return event_ms(ctx, ctx->ev0, ctx->ev1, ctx->query_ms);
 }
 
 int32_t apd_eval_transform(apd_eval_ctx *ctx, int64_t n64, const float *xyz, const double *T, float *out) {
@@ -1817,18 +1769,18 @@ int32_t apd_eval_transform(apd_eval_ctx *ctx, int64_t n64, const float *xyz, con
     const int n = (int)n64;
     ctx->transform_ms = 0.0;
     if (n == 0) return APD_OK;
-    EV_OK(ctx, hipSetDevice(ctx->device));
+    HIP_OK(ctx, hipSetDevice(ctx->device));
     if ((st = grow(ctx, ctx->q_xyz, (size_t)n * 12)) || (st = grow(ctx, ctx->x_out, (size_t)n * 12))) return st;
     hipStream_t s = ctx->stream;
-    EV_OK(ctx, hipMemcpyAsync(ctx->q_xyz.p, xyz, (size_t)n * 12, hipMemcpyDefault, s));
-    EV_OK(ctx, hipEventRecord(ctx->ev0, s));
+    HIP_OK(ctx, hipMemcpyAsync(ctx->q_xyz.p, xyz, (size_t)n * 12, hipMemcpyDefault, s));
+    HIP_OK(ctx, hipEventRecord(ctx->ev0, s));
     hipLaunchKernelGGL(k_transform, dim3(grid_for(n)), dim3(BLOCK), 0, s, (const float *)ctx->q_xyz.p, n, rows_of(T),
                        (float *)ctx->x_out.p);
-    EV_OK(ctx, hipGetLastError());
-    EV_OK(ctx, hipEventRecord(ctx->ev1, s));
-    EV_OK(ctx, hipMemcpyAsync(out, ctx->x_out.p, (size_t)n * 12, hipMemcpyDefault, s));
-    EV_OK(ctx, hipStreamSynchronize(s));
-    return elapsed(ctx, ctx->transform_ms);
+    HIP_OK(ctx, hipGetLastError());
+    HIP_OK(ctx, hipEventRecord(ctx->ev1, s));
+    HIP_OK(ctx, hipMemcpyAsync(out, ctx->x_out.p, (size_t)n * 12, hipMemcpyDefault, s));
+    HIP_OK(ctx, hipStreamSynchronize(s));
+    return event_ms(ctx, ctx->ev0, ctx->ev1, ctx->transform_ms);
 }
 
 // uploads the source once; reg_sums then evaluates a transform: the fused kernel, the fold, 19 doubles back
@@ -1839,7 +1791,7 @@ static int reg_upload(apd_eval_ctx *ctx, int n, const float *xyz) {
         (st = grow(ctx, ctx->g_part, (size_t)std::max(nblocks, 1) * APD_REG_SUMS * 8)) ||
         (st = grow(ctx, ctx->g_sums, APD_REG_SUMS * 8)) || (st = grow(ctx, ctx->small, 256)))
         return st;
-    if (n > 0) EV_OK(ctx, hipMemcpyAsync(ctx->q_xyz.p, xyz, (size_t)n * 12, hipMemcpyDefault, ctx->stream));
+    if (n > 0) HIP_OK(ctx, hipMemcpyAsync(ctx->q_xyz.p, xyz, (size_t)n * 12, hipMemcpyDefault, ctx->stream));
     ctx->reg_eval_ms = ctx->reg_fold_ms = ctx->reg_solve_ms = 0.0;
     ctx->reg_evaluations = 0;
     return APD_OK;
@@ -1848,21 +1800,21 @@ static int reg_upload(apd_eval_ctx *ctx, int n, const float *xyz) {
 static int reg_sums(apd_eval_ctx *ctx, int n, const double *T, float max_corr, float bound_d2, double *m) {
     hipStream_t s = ctx->stream;
     const int nblocks = (n + APD_REG_BLOCK - 1) / APD_REG_BLOCK;
-    EV_OK(ctx, hipEventRecord(ctx->ev0, s));
+    HIP_OK(ctx, hipEventRecord(ctx->ev0, s));
     if (nblocks > 0)
         hipLaunchKernelGGL(k_reg_eval, dim3(nblocks), dim3(BLOCK), 0, s, ctx->tree, (const int *)ctx->t_idx_s.p,
                            (const uint32_t *)ctx->small.p, (const float *)ctx->q_xyz.p, n, rows_of(T), bound_d2, max_corr,
                            (double *)ctx->g_part.p);
-    EV_OK(ctx, hipEventRecord(ctx->ev1, s));
+    HIP_OK(ctx, hipEventRecord(ctx->ev1, s));
     hipLaunchKernelGGL(k_reg_fold, dim3(1), dim3(64), 0, s, (const double *)ctx->g_part.p, nblocks,
                        (double *)ctx->g_sums.p);
-    EV_OK(ctx, hipGetLastError());
-    EV_OK(ctx, hipEventRecord(ctx->ev2, s));
-    EV_OK(ctx, hipMemcpyAsync(m, ctx->g_sums.p, APD_REG_SUMS * 8, hipMemcpyDeviceToHost, s));
-    EV_OK(ctx, hipStreamSynchronize(s));
+    HIP_OK(ctx, hipGetLastError());
+    HIP_OK(ctx, hipEventRecord(ctx->ev2, s));
+    HIP_OK(ctx, hipMemcpyAsync(m, ctx->g_sums.p, APD_REG_SUMS * 8, hipMemcpyDeviceToHost, s));
+    HIP_OK(ctx, hipStreamSynchronize(s));
     float a = 0.0f, b = 0.0f;
-    EV_OK(ctx, hipEventElapsedTime(&a, ctx->ev0, ctx->ev1));
-    EV_OK(ctx, hipEventElapsedTime(&b, ctx->ev1, ctx->ev2));
+    HIP_OK(ctx, hipEventElapsedTime(&a, ctx->ev0, ctx->ev1));
+    HIP_OK(ctx, hipEventElapsedTime(&b, ctx->ev1, ctx->ev2));
     ctx->reg_eval_ms += (double)a;
     ctx->reg_fold_ms += (double)b;
     ++ctx->reg_evaluations;
@@ -1893,7 +1845,7 @@ int32_t apd_eval_register_sums(apd_eval_ctx *ctx, int64_t n64, const float *xyz,
         ctx->err = "apd_eval_register_sums: NULL output";
         return APD_EINVAL;
     }
-    EV_OK(ctx, hipSetDevice(ctx->device));
+    HIP_OK(ctx, hipSetDevice(ctx->device));
     if ((st = reg_upload(ctx, (int)n64, xyz))) return st;
     return reg_sums(ctx, (int)n64, T, max_corr, d2_bound(max_corr), sums);
 }
@@ -1909,7 +1861,7 @@ int32_t apd_eval_register(apd_eval_ctx *ctx, int64_t n64, const float *xyz, cons
         ctx->err = "apd_eval_register: NULL output, with_scale outside 0..1, max_iter outside 1..1000 or a bad eps";
         return APD_EINVAL;
     }
-    EV_OK(ctx, hipSetDevice(ctx->device));
+    HIP_OK(ctx, hipSetDevice(ctx->device));
     const int n = (int)n64;
     if ((st = reg_upload(ctx, n, xyz))) return st;
     const float bound = d2_bound(max_corr);
@@ -1959,13 +1911,13 @@ int32_t apd_eval_radius_thin(apd_eval_ctx *ctx, int64_t n64, const float *xyz, f
         ctx->err = "apd_eval_radius_thin: NULL output";
         return APD_EINVAL;
     }
-    EV_OK(ctx, hipSetDevice(ctx->device));
+    HIP_OK(ctx, hipSetDevice(ctx->device));
     const int n = (int)n64;
     ctx->thin_sort_ms = ctx->thin_rounds_ms = 0.0;
     ctx->thin_rounds = 0;
     unsigned long long kept = 0;
     if (n == 0) {
-        EV_OK(ctx, hipMemcpy(n_keep, &kept, 8, hipMemcpyDefault));
+        HIP_OK(ctx, hipMemcpy(n_keep, &kept, 8, hipMemcpyDefault));
         return APD_OK;
     }
     // q_dist holds the kept flags, q_aux their exclusive scan from byte 128 and the kept count at byte
@@ -1982,19 +1934,19 @@ int32_t apd_eval_radius_thin(apd_eval_ctx *ctx, int64_t n64, const float *xyz, f
     unsigned int *cnt = (unsigned int *)((char *)ctx->th_small.p + 128);  // THIN_BATCH + 1 words
     unsigned long long *counter = (unsigned long long *)((char *)ctx->q_aux.p + 64);
     hipStream_t s = ctx->stream;
-    EV_OK(ctx, hipMemcpyAsync(ctx->q_xyz.p, xyz, (size_t)n * 12, hipMemcpyDefault, s));
-    if (rank) EV_OK(ctx, hipMemcpyAsync(ctx->th_rank.p, rank, (size_t)n * 4, hipMemcpyDefault, s));
-    EV_OK(ctx, hipEventRecord(ctx->ev0, s));
-    EV_OK(ctx, hipMemsetAsync(bounds, 0xFF, 12, s));
-    EV_OK(ctx, hipMemsetAsync(bounds + 3, 0, 12, s));
-    EV_OK(ctx, hipMemsetAsync(n_finite, 0, 8, s));
+    HIP_OK(ctx, hipMemcpyAsync(ctx->q_xyz.p, xyz, (size_t)n * 12, hipMemcpyDefault, s));
+    if (rank) HIP_OK(ctx, hipMemcpyAsync(ctx->th_rank.p, rank, (size_t)n * 4, hipMemcpyDefault, s));
+    HIP_OK(ctx, hipEventRecord(ctx->ev0, s));
+    HIP_OK(ctx, hipMemsetAsync(bounds, 0xFF, 12, s));
+    HIP_OK(ctx, hipMemsetAsync(bounds + 3, 0, 12, s));
+    HIP_OK(ctx, hipMemsetAsync(n_finite, 0, 8, s));
     hipLaunchKernelGGL(k_bounds, dim3(grid_capped(n)), dim3(BLOCK), 0, s, (const float *)ctx->q_xyz.p, n, bounds);
-    EV_OK(ctx, hipGetLastError());
+    HIP_OK(ctx, hipGetLastError());
     uint32_t hb[6];
-    EV_OK(ctx, hipMemcpyAsync(hb, bounds, 24, hipMemcpyDeviceToHost, s));
-    EV_OK(ctx, hipStreamSynchronize(s));
+    HIP_OK(ctx, hipMemcpyAsync(hb, bounds, 24, hipMemcpyDeviceToHost, s));
+    HIP_OK(ctx, hipStreamSynchronize(s));
     if (hb[0] == 0xFFFFFFFFu) {  // no finite point
-        EV_OK(ctx, hipMemcpy(n_keep, &kept, 8, hipMemcpyDefault));
+        HIP_OK(ctx, hipMemcpy(n_keep, &kept, 8, hipMemcpyDefault));
         return APD_OK;
     }
     // the cell index is monotone in the coordinate, so the occupied cells span cell(min) .. cell(max)
@@ -2013,11 +1965,11 @@ int32_t apd_eval_radius_thin(apd_eval_ctx *ctx, int64_t n64, const float *xyz, f
     }
     hipLaunchKernelGGL(k_thin_keys, dim3(grid_for(n)), dim3(BLOCK), 0, s, (const float *)ctx->q_xyz.p, n, g,
                        (uint64_t *)ctx->q_keys.p, (int *)ctx->q_idx.p, n_finite);
-    EV_OK(ctx, hipGetLastError());
+    HIP_OK(ctx, hipGetLastError());
     if ((st = sort_pairs(ctx, ctx->q_keys, ctx->q_keys_s, ctx->q_idx, ctx->q_idx_s, n))) return st;
     unsigned long long nf64 = 0;
-    EV_OK(ctx, hipMemcpyAsync(&nf64, n_finite, 8, hipMemcpyDeviceToHost, s));
-    EV_OK(ctx, hipStreamSynchronize(s));
+    HIP_OK(ctx, hipMemcpyAsync(&nf64, n_finite, 8, hipMemcpyDeviceToHost, s));
+    HIP_OK(ctx, hipStreamSynchronize(s));
     const int nf = (int)nf64;  // >= 1: the bounds saw a finite point
     if ((st = grow(ctx, ctx->th_pts, (size_t)nf * 16)) ||
         (st = grow(ctx, ctx->th_runs, (size_t)nf * THIN_RUNS * sizeof(int2))) ||
@@ -2034,9 +1986,9 @@ int32_t apd_eval_radius_thin(apd_eval_ctx *ctx, int64_t n64, const float *xyz, f
                        (float4 *)ctx->th_pts.p);
     hipLaunchKernelGGL(k_thin_runs, dim3(grid_for(nf)), dim3(BLOCK), 0, s, (const uint64_t *)ctx->q_keys_s.p, nf,
                        (int2 *)ctx->th_runs.p);
-    EV_OK(ctx, hipMemsetAsync(state, THIN_UNDECIDED, (size_t)nf, s));
-    EV_OK(ctx, hipGetLastError());
-    EV_OK(ctx, hipEventRecord(ctx->ev1, s));
+    HIP_OK(ctx, hipMemsetAsync(state, THIN_UNDECIDED, (size_t)nf, s));
+    HIP_OK(ctx, hipGetLastError());
+    HIP_OK(ctx, hipEventRecord(ctx->ev1, s));
 
     // Rounds until no point is undecided. Round r reads the worklist lists[r & 1] (round 0: every
     // position) and writes lists[(r + 1) & 1]; a batch of rounds shares one read-back of its counters,
@@ -2046,16 +1998,16 @@ int32_t apd_eval_radius_thin(apd_eval_ctx *ctx, int64_t n64, const float *xyz, f
     int round = 0;
     while (m > 0) {
         const int batch = (int)m > THIN_BATCH_BELOW ? 1 : THIN_BATCH;
-        EV_OK(ctx, hipMemsetD32Async((hipDeviceptr_t)cnt, (int)m, 1, s));
-        EV_OK(ctx, hipMemsetAsync(cnt + 1, 0, (size_t)batch * 4, s));
+        HIP_OK(ctx, hipMemsetD32Async((hipDeviceptr_t)cnt, (int)m, 1, s));
+        HIP_OK(ctx, hipMemsetAsync(cnt + 1, 0, (size_t)batch * 4, s));
         for (int k = 0; k < batch; ++k, ++round)
             hipLaunchKernelGGL(k_thin_round, dim3(grid_for(m)), dim3(BLOCK), 0, s, pts, idx_s, runs, nf, r2,
                                round == 0 ? (const int *)nullptr : (const int *)lists[round & 1],
                                (const unsigned int *)(cnt + k), state, lists[(round + 1) & 1], cnt + k + 1);
-        EV_OK(ctx, hipGetLastError());
+        HIP_OK(ctx, hipGetLastError());
         unsigned int hc[THIN_BATCH];
-        EV_OK(ctx, hipMemcpyAsync(hc, cnt + 1, (size_t)batch * 4, hipMemcpyDeviceToHost, s));
-        EV_OK(ctx, hipStreamSynchronize(s));
+        HIP_OK(ctx, hipMemcpyAsync(hc, cnt + 1, (size_t)batch * 4, hipMemcpyDeviceToHost, s));
+        HIP_OK(ctx, hipStreamSynchronize(s));
         int used = batch;  // the rounds of this batch up to the first that left nothing
         for (int k = 0; k < batch; ++k)
             if (hc[k] == 0) {
@@ -2071,27 +2023,23 @@ int32_t apd_eval_radius_thin(apd_eval_ctx *ctx, int64_t n64, const float *xyz, f
     }
 
     int *flag = (int *)ctx->q_dist.p, *pos = (int *)ctx->q_aux.p + 32, *keep = (int *)ctx->q_keys.p;
-    EV_OK(ctx, hipMemsetAsync(flag, 0, (size_t)n * 4, s));
+    HIP_OK(ctx, hipMemsetAsync(flag, 0, (size_t)n * 4, s));
     hipLaunchKernelGGL(k_thin_flags, dim3(grid_for(nf)), dim3(BLOCK), 0, s, (const uint8_t *)state, idx_s, nf, flag);
-    EV_OK(ctx, hipGetLastError());
+    HIP_OK(ctx, hipGetLastError());
     size_t tb = 0;
-    EV_OK(ctx, rocprim::exclusive_scan(nullptr, tb, flag, pos, 0, (size_t)n, rocprim::plus<int>(), s));
+    HIP_OK(ctx, rocprim::exclusive_scan(nullptr, tb, flag, pos, 0, (size_t)n, rocprim::plus<int>(), s));
     if ((st = grow(ctx, ctx->sort_tmp, tb))) return st;
-    EV_OK(ctx, rocprim::exclusive_scan(ctx->sort_tmp.p, tb, flag, pos, 0, (size_t)n, rocprim::plus<int>(), s));
+    HIP_OK(ctx, rocprim::exclusive_scan(ctx->sort_tmp.p, tb, flag, pos, 0, (size_t)n, rocprim::plus<int>(), s));
     hipLaunchKernelGGL(k_voxel_compact, dim3(grid_for(n)), dim3(BLOCK), 0, s, (const int *)flag, (const int *)pos, n,
                        keep, counter);
-    EV_OK(ctx, hipGetLastError());
-    EV_OK(ctx, hipEventRecord(ctx->ev2, s));
-    EV_OK(ctx, hipMemcpyAsync(&kept, counter, 8, hipMemcpyDeviceToHost, s));
-    EV_OK(ctx, hipStreamSynchronize(s));
-    if (kept > 0) EV_OK(ctx, hipMemcpy(keep_idx, keep, (size_t)kept * 4, hipMemcpyDefault));
-    EV_OK(ctx, hipMemcpy(n_keep, &kept, 8, hipMemcpyDefault));
-    float f = 0.0f;
-    EV_OK(ctx, hipEventElapsedTime(&f, ctx->ev0, ctx->ev1));
-    ctx->thin_sort_ms = (double)f;
-    EV_OK(ctx, hipEventElapsedTime(&f, ctx->ev1, ctx->ev2));
-    ctx->thin_rounds_ms = (double)f;
-    return APD_OK;
+    HIP_OK(ctx, hipGetLastError());
+    HIP_OK(ctx, hipEventRecord(ctx->ev2, s));
+    HIP_OK(ctx, hipMemcpyAsync(&kept, counter, 8, hipMemcpyDeviceToHost, s));
+    HIP_OK(ctx, hipStreamSynchronize(s));
+    if (kept > 0) HIP_OK(ctx, hipMemcpy(keep_idx, keep, (size_t)kept * 4, hipMemcpyDefault));
+    HIP_OK(ctx, hipMemcpy(n_keep, &kept, 8, hipMemcpyDefault));
+    if ((st = event_ms(ctx, ctx->ev0, ctx->ev1, ctx->thin_sort_ms))) return st;
+    return event_ms(ctx, ctx->ev1, ctx->ev2, ctx->thin_rounds_ms);
 }
 
 int32_t apd_eval_get_thin_timing(apd_eval_ctx *ctx, double *sort_ms, double *rounds_ms, int32_t *rounds) {
@@ -2131,29 +2079,29 @@ int32_t apd_eval_obs_mask(apd_eval_ctx *ctx, int64_t n64, const float *xyz, cons
         return APD_EINVAL;
     }
     g.res = res;
-    EV_OK(ctx, hipSetDevice(ctx->device));
+    HIP_OK(ctx, hipSetDevice(ctx->device));
     const int n = (int)n64;
     ctx->mask_ms = 0.0;
     hipStream_t s = ctx->stream;
     if (ctx->mask_src != mask || memcmp(ctx->mask_dims, dims, 12) != 0) {
         ctx->mask_src = nullptr;
         if ((st = grow(ctx, ctx->m_mask, (size_t)total))) return st;
-        EV_OK(ctx, hipMemcpyAsync(ctx->m_mask.p, mask, (size_t)total, hipMemcpyDefault, s));
-        EV_OK(ctx, hipStreamSynchronize(s));
+        HIP_OK(ctx, hipMemcpyAsync(ctx->m_mask.p, mask, (size_t)total, hipMemcpyDefault, s));
+        HIP_OK(ctx, hipStreamSynchronize(s));
         ctx->mask_src = mask;
         memcpy(ctx->mask_dims, dims, 12);
     }
     if (n == 0) return APD_OK;
     if ((st = grow(ctx, ctx->q_xyz, (size_t)n * 12)) || (st = grow(ctx, ctx->d_flag, (size_t)n))) return st;
-    EV_OK(ctx, hipMemcpyAsync(ctx->q_xyz.p, xyz, (size_t)n * 12, hipMemcpyDefault, s));
-    EV_OK(ctx, hipEventRecord(ctx->ev0, s));
+    HIP_OK(ctx, hipMemcpyAsync(ctx->q_xyz.p, xyz, (size_t)n * 12, hipMemcpyDefault, s));
+    HIP_OK(ctx, hipEventRecord(ctx->ev0, s));
     hipLaunchKernelGGL(k_obs_mask, dim3(grid_for(n)), dim3(BLOCK), 0, s, (const float *)ctx->q_xyz.p, n, g,
                        (const uint8_t *)ctx->m_mask.p, (uint8_t *)ctx->d_flag.p);
-    EV_OK(ctx, hipGetLastError());
-    EV_OK(ctx, hipEventRecord(ctx->ev1, s));
-    EV_OK(ctx, hipMemcpyAsync(inside, ctx->d_flag.p, (size_t)n, hipMemcpyDefault, s));
-    EV_OK(ctx, hipStreamSynchronize(s));
-    return elapsed(ctx, ctx->mask_ms);
+    HIP_OK(ctx, hipGetLastError());
+    HIP_OK(ctx, hipEventRecord(ctx->ev1, s));
+    HIP_OK(ctx, hipMemcpyAsync(inside, ctx->d_flag.p, (size_t)n, hipMemcpyDefault, s));
+    HIP_OK(ctx, hipStreamSynchronize(s));
+    return event_ms(ctx, ctx->ev0, ctx->ev1, ctx->mask_ms);
 }
 
 int32_t apd_eval_half_space(apd_eval_ctx *ctx, int64_t n64, const float *xyz, const double P[4], uint8_t *above) {
@@ -2167,20 +2115,20 @@ int32_t apd_eval_half_space(apd_eval_ctx *ctx, int64_t n64, const float *xyz, co
     const int n = (int)n64;
     ctx->half_space_ms = 0.0;
     if (n == 0) return APD_OK;
-    EV_OK(ctx, hipSetDevice(ctx->device));
+    HIP_OK(ctx, hipSetDevice(ctx->device));
     if ((st = grow(ctx, ctx->q_xyz, (size_t)n * 12)) || (st = grow(ctx, ctx->d_flag, (size_t)n))) return st;
     Plane4 pl;
     for (int k = 0; k < 4; ++k) pl.P[k] = P[k];
     hipStream_t s = ctx->stream;
-    EV_OK(ctx, hipMemcpyAsync(ctx->q_xyz.p, xyz, (size_t)n * 12, hipMemcpyDefault, s));
-    EV_OK(ctx, hipEventRecord(ctx->ev0, s));
+    HIP_OK(ctx, hipMemcpyAsync(ctx->q_xyz.p, xyz, (size_t)n * 12, hipMemcpyDefault, s));
+    HIP_OK(ctx, hipEventRecord(ctx->ev0, s));
     hipLaunchKernelGGL(k_half_space, dim3(grid_for(n)), dim3(BLOCK), 0, s, (const float *)ctx->q_xyz.p, n, pl,
                        (uint8_t *)ctx->d_flag.p);
-    EV_OK(ctx, hipGetLastError());
-    EV_OK(ctx, hipEventRecord(ctx->ev1, s));
-    EV_OK(ctx, hipMemcpyAsync(above, ctx->d_flag.p, (size_t)n, hipMemcpyDefault, s));
-    EV_OK(ctx, hipStreamSynchronize(s));
-    return elapsed(ctx, ctx->half_space_ms);
+    HIP_OK(ctx, hipGetLastError());
+    HIP_OK(ctx, hipEventRecord(ctx->ev1, s));
+    HIP_OK(ctx, hipMemcpyAsync(above, ctx->d_flag.p, (size_t)n, hipMemcpyDefault, s));
+    HIP_OK(ctx, hipStreamSynchronize(s));
+    return event_ms(ctx, ctx->ev0, ctx->ev1, ctx->half_space_ms);
 }
 
 int32_t apd_eval_masked_stats(apd_eval_ctx *ctx, int64_t n64, const float *dist, const uint8_t *flag, float limit,
@@ -2198,7 +2146,7 @@ int32_t apd_eval_masked_stats(apd_eval_ctx *ctx, int64_t n64, const float *dist,
     if (sum) *sum = 0.0;
     if (median) *median = 0.0;
     if (n == 0) return APD_OK;
-    EV_OK(ctx, hipSetDevice(ctx->device));
+    HIP_OK(ctx, hipSetDevice(ctx->device));
     const int nblocks = (int)((n64 + APD_REG_BLOCK - 1) / APD_REG_BLOCK);
     // s_dist: the distances; q_keys / q_keys_s: the 32-bit sort keys and their sorted copy;
     // st_out: the sum at byte 0, the count at byte 8
@@ -2210,32 +2158,32 @@ int32_t apd_eval_masked_stats(apd_eval_ctx *ctx, int64_t n64, const float *dist,
     double *out = (double *)ctx->st_out.p;
     unsigned long long *cnt = (unsigned long long *)ctx->st_out.p + 1;
     hipStream_t s = ctx->stream;
-    EV_OK(ctx, hipMemcpyAsync(ctx->s_dist.p, dist, (size_t)n * 4, hipMemcpyDefault, s));
-    if (flag) EV_OK(ctx, hipMemcpyAsync(ctx->d_flag.p, flag, (size_t)n, hipMemcpyDefault, s));
-    EV_OK(ctx, hipEventRecord(ctx->ev0, s));
-    EV_OK(ctx, hipMemsetAsync(cnt, 0, 8, s));
+    HIP_OK(ctx, hipMemcpyAsync(ctx->s_dist.p, dist, (size_t)n * 4, hipMemcpyDefault, s));
+    if (flag) HIP_OK(ctx, hipMemcpyAsync(ctx->d_flag.p, flag, (size_t)n, hipMemcpyDefault, s));
+    HIP_OK(ctx, hipEventRecord(ctx->ev0, s));
+    HIP_OK(ctx, hipMemsetAsync(cnt, 0, 8, s));
     hipLaunchKernelGGL(k_stats_block, dim3(nblocks), dim3(BLOCK), 0, s, (const float *)ctx->s_dist.p,
                        flag ? (const uint8_t *)ctx->d_flag.p : (const uint8_t *)nullptr, n, limit,
                        (double *)ctx->st_part.p, keys, cnt);
     hipLaunchKernelGGL(k_stats_fold, dim3(1), dim3(64), 0, s, (const double *)ctx->st_part.p, nblocks, out);
-    EV_OK(ctx, hipGetLastError());
+    HIP_OK(ctx, hipGetLastError());
     size_t tb = 0;
-    EV_OK(ctx, rocprim::radix_sort_keys(nullptr, tb, keys, keys_s, (size_t)n, 0, 32, s));
+    HIP_OK(ctx, rocprim::radix_sort_keys(nullptr, tb, keys, keys_s, (size_t)n, 0, 32, s));
     if ((st = grow(ctx, ctx->sort_tmp, tb))) return st;
-    EV_OK(ctx, rocprim::radix_sort_keys(ctx->sort_tmp.p, tb, keys, keys_s, (size_t)n, 0, 32, s));
-    EV_OK(ctx, hipEventRecord(ctx->ev1, s));
+    HIP_OK(ctx, rocprim::radix_sort_keys(ctx->sort_tmp.p, tb, keys, keys_s, (size_t)n, 0, 32, s));
+    HIP_OK(ctx, hipEventRecord(ctx->ev1, s));
     struct {
         double sum;
         unsigned long long count;
     } h{};
-    EV_OK(ctx, hipMemcpyAsync(&h, ctx->st_out.p, 16, hipMemcpyDeviceToHost, s));
-    EV_OK(ctx, hipStreamSynchronize(s));
+    HIP_OK(ctx, hipMemcpyAsync(&h, ctx->st_out.p, 16, hipMemcpyDeviceToHost, s));
+    HIP_OK(ctx, hipStreamSynchronize(s));
     double med = 0.0;
     if (h.count > 0) {
         const size_t m = (size_t)h.count, a = (m - 1) / 2, b = m / 2;  // a == b for an odd count
         uint32_t mid[2];
-        EV_OK(ctx, hipMemcpy(&mid[0], keys_s + a, 4, hipMemcpyDeviceToHost));
-        EV_OK(ctx, hipMemcpy(&mid[1], keys_s + b, 4, hipMemcpyDeviceToHost));
+        HIP_OK(ctx, hipMemcpy(&mid[0], keys_s + a, 4, hipMemcpyDeviceToHost));
+        HIP_OK(ctx, hipMemcpy(&mid[1], keys_s + b, 4, hipMemcpyDeviceToHost));
         float v[2];
         for (int k = 0; k < 2; ++k) {
             const uint32_t u = (mid[k] & 0x80000000u) ? (mid[k] & 0x7FFFFFFFu) : ~mid[k];
@@ -2246,7 +2194,7 @@ int32_t apd_eval_masked_stats(apd_eval_ctx *ctx, int64_t n64, const float *dist,
     if (count) *count = (int64_t)h.count;
     if (sum) *sum = h.sum;
     if (median) *median = med;
-    return elapsed(ctx, ctx->stats_ms);
+    return event_ms(ctx, ctx->ev0, ctx->ev1, ctx->stats_ms);
 }
 
 int32_t apd_eval_get_dtu_timing(apd_eval_ctx *ctx, double *mask_ms, double *half_space_ms, double *stats_ms) {

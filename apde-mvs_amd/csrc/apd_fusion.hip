@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "../../include/apd_fusion.h"
+#include "apd_host.h"
 
 namespace {
 
@@ -234,45 +235,36 @@ __global__ void __launch_bounds__(256) k_tat_levels(const DevView *views, const 
 
 }  // namespace
 
-struct apd_fusion_ctx {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    std::string err;
-    std::vector<void *> bufs;  // per-view device arrays
-    DevView *d_views = nullptr;
-    apd_camera *d_cams = nullptr;
+struct apd_fusion_ctx : DevCtx {
+    apd_fusion_ctx() : DevCtx("apd_fusion") {}
+    std::vector<DevBuf> bufs;  // per-view device arrays: depth, normal, weak, confidence of view 0, of view 1, ...
+    DevBuf d_views, d_cams;    // DevView[views], apd_camera[views]
     std::vector<DevView> views;
-    void *out_buf = nullptr;
-    size_t out_bytes = 0;
+    DevBuf out_buf;
 };
 
-#define FUS_OK(ctx, call)                                                                          \
-    do {                                                                                           \
-        hipError_t e_ = (call);                                                                    \
-        if (e_ != hipSuccess) {                                                                    \
-            (ctx)->err = std::string(#call) + ": " + hipGetErrorString(e_);                        \
-            return APD_EDEVICE;                                                                    \
-        }                                                                                          \
-    } while (0)
+// A failed allocation here keeps the status and the words it has always had (APD_EDEVICE and the
+// runtime's own message after `call`, the allocation as it once stood in the text), not grow()'s.
+static int alloc(apd_fusion_ctx *ctx, DevBuf &b, size_t bytes, const char *call) {
+    const hipError_t e = reallocate(ctx, b, bytes);
+    if (e != hipSuccess) {
+        ctx->err = std::string(call) + ": " + hipGetErrorString(e);
+        return APD_EDEVICE;
+    }
+    return APD_OK;
+}
 
 static void release_views(apd_fusion_ctx *ctx) {
-    for (void *p : ctx->bufs) (void)hipFree(p);
+    for (DevBuf &b : ctx->bufs) release(ctx, b);
     ctx->bufs.clear();
-    if (ctx->d_views) (void)hipFree(ctx->d_views);
-    if (ctx->d_cams) (void)hipFree(ctx->d_cams);
-    ctx->d_views = nullptr;
-    ctx->d_cams = nullptr;
+    release(ctx, ctx->d_views);
+    release(ctx, ctx->d_cams);
     ctx->views.clear();
 }
 
 static int ensure_out(apd_fusion_ctx *ctx, size_t bytes) {
-    if (ctx->out_bytes >= bytes) return APD_OK;
-    if (ctx->out_buf) (void)hipFree(ctx->out_buf);
-    ctx->out_buf = nullptr;
-    ctx->out_bytes = 0;
-    FUS_OK(ctx, hipMalloc(&ctx->out_buf, bytes));
-    ctx->out_bytes = bytes;
-    return APD_OK;
+    if (ctx->out_buf.bytes >= bytes) return APD_OK;
+    return alloc(ctx, ctx->out_buf, bytes, "hipMalloc(&ctx->out_buf, bytes)");
 }
 
 static int check_srcs(apd_fusion_ctx *ctx, int ref, int num_src, const int32_t *src, SrcList &sl) {
@@ -294,25 +286,14 @@ static int check_srcs(apd_fusion_ctx *ctx, int ref, int num_src, const int32_t *
 extern "C" {
 
 apd_fusion_ctx *apd_fusion_create(int32_t device) {
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || device < 0 || device >= n) return nullptr;
-    if (hipSetDevice(device) != hipSuccess) return nullptr;
-    auto *ctx = new apd_fusion_ctx();
-    ctx->device = device;
-    if (hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking) != hipSuccess) {
-        delete ctx;
-        return nullptr;
-    }
-    return ctx;
+    return open_ctx<apd_fusion_ctx>(device);
 }
 
 void apd_fusion_destroy(apd_fusion_ctx *ctx) {
     if (!ctx) return;
     (void)hipSetDevice(ctx->device);
-    release_views(ctx);
-    if (ctx->out_buf) (void)hipFree(ctx->out_buf);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
-    delete ctx;
+    delete ctx;  // the buffers with it
 }
 
 const char *apd_fusion_last_error(const apd_fusion_ctx *ctx) {
@@ -321,10 +302,12 @@ const char *apd_fusion_last_error(const apd_fusion_ctx *ctx) {
 
 int32_t apd_fusion_set_views(apd_fusion_ctx *ctx, int32_t num_views, const apd_fusion_view *views) {
     if (!ctx) return APD_EINVAL;
-    FUS_OK(ctx, hipSetDevice(ctx->device));
+    HIP_OK(ctx, hipSetDevice(ctx->device));
     release_views(ctx);
     if (num_views <= 0 || !views) { ctx->err = "apd_fusion_set_views: no views"; return APD_EINVAL; }
     std::vector<apd_camera> cams(num_views);
+    ctx->bufs.resize(4 * (size_t)num_views);
+    int st;
     for (int i = 0; i < num_views; ++i) {
         const apd_fusion_view &v = views[i];
         if (v.width <= 0 || v.height <= 0 || !v.depth || !v.normal || !v.weak ||
@@ -335,31 +318,32 @@ int32_t apd_fusion_set_views(apd_fusion_ctx *ctx, int32_t num_views, const apd_f
         const size_t npx = (size_t)v.width * v.height;
         // confidence: W*H bytes + the zero tail read by at<float>(r, c) for the last row (<= 4W+4)
         const size_t conf_bytes = npx + 4 * (size_t)v.width + 8;
-        void *dd = nullptr, *dn = nullptr, *dw = nullptr, *dc = nullptr;
-        FUS_OK(ctx, hipMalloc(&dd, npx * 4));
-        ctx->bufs.push_back(dd);
-        FUS_OK(ctx, hipMalloc(&dn, npx * 12));
-        ctx->bufs.push_back(dn);
-        FUS_OK(ctx, hipMalloc(&dw, npx));
-        ctx->bufs.push_back(dw);
-        FUS_OK(ctx, hipMalloc(&dc, conf_bytes));
-        ctx->bufs.push_back(dc);
-        FUS_OK(ctx, hipMemcpyAsync(dd, v.depth, npx * 4, hipMemcpyHostToDevice, ctx->stream));
-        FUS_OK(ctx, hipMemcpyAsync(dn, v.normal, npx * 12, hipMemcpyHostToDevice, ctx->stream));
-        FUS_OK(ctx, hipMemcpyAsync(dw, v.weak, npx, hipMemcpyHostToDevice, ctx->stream));
-        FUS_OK(ctx, hipMemsetAsync(dc, 0, conf_bytes, ctx->stream));
-        if (v.confidence) FUS_OK(ctx, hipMemcpyAsync(dc, v.confidence, npx, hipMemcpyHostToDevice, ctx->stream));
+        DevBuf *b = &ctx->bufs[4 * (size_t)i];
+        if ((st = alloc(ctx, b[0], npx * 4, "hipMalloc(&dd, npx * 4)")) ||
+            (st = alloc(ctx, b[1], npx * 12, "hipMalloc(&dn, npx * 12)")) ||
+            (st = alloc(ctx, b[2], npx, "hipMalloc(&dw, npx)")) ||
+            (st = alloc(ctx, b[3], conf_bytes, "hipMalloc(&dc, conf_bytes)")))
+            return st;
+        void *dd = b[0].p, *dn = b[1].p, *dw = b[2].p, *dc = b[3].p;
+        HIP_OK(ctx, hipMemcpyAsync(dd, v.depth, npx * 4, hipMemcpyHostToDevice, ctx->stream));
+        HIP_OK(ctx, hipMemcpyAsync(dn, v.normal, npx * 12, hipMemcpyHostToDevice, ctx->stream));
+        HIP_OK(ctx, hipMemcpyAsync(dw, v.weak, npx, hipMemcpyHostToDevice, ctx->stream));
+        HIP_OK(ctx, hipMemsetAsync(dc, 0, conf_bytes, ctx->stream));
+        if (v.confidence) HIP_OK(ctx, hipMemcpyAsync(dc, v.confidence, npx, hipMemcpyHostToDevice, ctx->stream));
         ctx->views.push_back(DevView{v.width, v.height, (const float *)dd, (const float *)dn, (const uint8_t *)dw,
                                      (const uint8_t *)dc});
         cams[i] = v.camera;
     }
-    FUS_OK(ctx, hipMalloc(&ctx->d_views, sizeof(DevView) * num_views));
-    FUS_OK(ctx, hipMalloc(&ctx->d_cams, sizeof(apd_camera) * num_views));
-    FUS_OK(ctx, hipMemcpyAsync(ctx->d_views, ctx->views.data(), sizeof(DevView) * num_views, hipMemcpyHostToDevice,
+    if ((st = alloc(ctx, ctx->d_views, sizeof(DevView) * num_views,
+                    "hipMalloc(&ctx->d_views, sizeof(DevView) * num_views)")) ||
+        (st = alloc(ctx, ctx->d_cams, sizeof(apd_camera) * num_views,
+                    "hipMalloc(&ctx->d_cams, sizeof(apd_camera) * num_views)")))
+        return st;
+    HIP_OK(ctx, hipMemcpyAsync(ctx->d_views.p, ctx->views.data(), sizeof(DevView) * num_views, hipMemcpyHostToDevice,
                                ctx->stream));
-    FUS_OK(ctx, hipMemcpyAsync(ctx->d_cams, cams.data(), sizeof(apd_camera) * num_views, hipMemcpyHostToDevice,
+    HIP_OK(ctx, hipMemcpyAsync(ctx->d_cams.p, cams.data(), sizeof(apd_camera) * num_views, hipMemcpyHostToDevice,
                                ctx->stream));
-    FUS_OK(ctx, hipStreamSynchronize(ctx->stream));
+    HIP_OK(ctx, hipStreamSynchronize(ctx->stream));
     return APD_OK;
 }
 
@@ -369,16 +353,16 @@ int32_t apd_fusion_weak_filter(apd_fusion_ctx *ctx, int32_t ref, float q_view, u
     int st = check_srcs(ctx, ref, 0, nullptr, sl);
     if (st) return st;
     if (!skip) { ctx->err = "apd_fusion_weak_filter: NULL output"; return APD_EINVAL; }
-    FUS_OK(ctx, hipSetDevice(ctx->device));
+    HIP_OK(ctx, hipSetDevice(ctx->device));
     const DevView &rv = ctx->views[ref];
     const size_t npx = (size_t)rv.W * rv.H;
     if ((st = ensure_out(ctx, npx))) return st;
     const int blocks = (int)((npx + 255) / 256);
-    hipLaunchKernelGGL(k_weak_filter, dim3(blocks), dim3(256), 0, ctx->stream, ctx->d_views, ctx->d_cams,
-                       (int)ctx->views.size(), ref, q_view, (uint8_t *)ctx->out_buf);
-    FUS_OK(ctx, hipGetLastError());
-    FUS_OK(ctx, hipMemcpyAsync(skip, ctx->out_buf, npx, hipMemcpyDeviceToHost, ctx->stream));
-    FUS_OK(ctx, hipStreamSynchronize(ctx->stream));
+    hipLaunchKernelGGL(k_weak_filter, dim3(blocks), dim3(256), 0, ctx->stream, (const DevView *)ctx->d_views.p,
+                       (const apd_camera *)ctx->d_cams.p, (int)ctx->views.size(), ref, q_view, (uint8_t *)ctx->out_buf.p);
+    HIP_OK(ctx, hipGetLastError());
+    HIP_OK(ctx, hipMemcpyAsync(skip, ctx->out_buf.p, npx, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_OK(ctx, hipStreamSynchronize(ctx->stream));
     return APD_OK;
 }
 
@@ -389,21 +373,21 @@ int32_t apd_fusion_consistency(apd_fusion_ctx *ctx, int32_t ref, int32_t num_src
     int st = check_srcs(ctx, ref, num_src, src, sl);
     if (st) return st;
     if (!src_pix || !err_rel || !cos_angle) { ctx->err = "apd_fusion_consistency: NULL output"; return APD_EINVAL; }
-    FUS_OK(ctx, hipSetDevice(ctx->device));
+    HIP_OK(ctx, hipSetDevice(ctx->device));
     const DevView &rv = ctx->views[ref];
     const size_t npx = (size_t)rv.W * rv.H, n = npx * (size_t)num_src;
     if (n == 0) return APD_OK;
     if ((st = ensure_out(ctx, n * 12))) return st;
-    int32_t *d_pix = (int32_t *)ctx->out_buf;
+    int32_t *d_pix = (int32_t *)ctx->out_buf.p;
     float *d_er = (float *)(d_pix + n), *d_q = d_er + n;
     const int blocks = (int)((npx + 255) / 256);
-    hipLaunchKernelGGL(k_consistency, dim3(blocks), dim3(256), 0, ctx->stream, ctx->d_views, ctx->d_cams, ref, sl,
-                       q_angle, d_pix, d_er, d_q);
-    FUS_OK(ctx, hipGetLastError());
-    FUS_OK(ctx, hipMemcpyAsync(src_pix, d_pix, n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    FUS_OK(ctx, hipMemcpyAsync(err_rel, d_er, n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    FUS_OK(ctx, hipMemcpyAsync(cos_angle, d_q, n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    FUS_OK(ctx, hipStreamSynchronize(ctx->stream));
+    hipLaunchKernelGGL(k_consistency, dim3(blocks), dim3(256), 0, ctx->stream, (const DevView *)ctx->d_views.p,
+                       (const apd_camera *)ctx->d_cams.p, ref, sl, q_angle, d_pix, d_er, d_q);
+    HIP_OK(ctx, hipGetLastError());
+    HIP_OK(ctx, hipMemcpyAsync(src_pix, d_pix, n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_OK(ctx, hipMemcpyAsync(err_rel, d_er, n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_OK(ctx, hipMemcpyAsync(cos_angle, d_q, n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_OK(ctx, hipStreamSynchronize(ctx->stream));
     return APD_OK;
 }
 
@@ -414,7 +398,7 @@ int32_t apd_fusion_tat_levels(apd_fusion_ctx *ctx, int32_t ref, int32_t num_src,
     int st = check_srcs(ctx, ref, num_src, src, sl);
     if (st) return st;
     if (!src_pix || !level) { ctx->err = "apd_fusion_tat_levels: NULL output"; return APD_EINVAL; }
-    FUS_OK(ctx, hipSetDevice(ctx->device));
+    HIP_OK(ctx, hipSetDevice(ctx->device));
     LevelCuts cuts{};
     if (q_k)
         for (int k = 0; k <= num_src; ++k) cuts.q[k] = q_k[k];
@@ -422,15 +406,15 @@ int32_t apd_fusion_tat_levels(apd_fusion_ctx *ctx, int32_t ref, int32_t num_src,
     const size_t npx = (size_t)rv.W * rv.H, n = npx * (size_t)num_src;
     if (n == 0) return APD_OK;
     if ((st = ensure_out(ctx, n * 5))) return st;
-    int32_t *d_pix = (int32_t *)ctx->out_buf;
+    int32_t *d_pix = (int32_t *)ctx->out_buf.p;
     uint8_t *d_lv = (uint8_t *)(d_pix + n);
     const int blocks = (int)((npx + 255) / 256);
-    hipLaunchKernelGGL(k_tat_levels, dim3(blocks), dim3(256), 0, ctx->stream, ctx->d_views, ctx->d_cams, ref, sl,
-                       dist_base, depth_base, q_k ? 1 : 0, cuts, d_pix, d_lv);
-    FUS_OK(ctx, hipGetLastError());
-    FUS_OK(ctx, hipMemcpyAsync(src_pix, d_pix, n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    FUS_OK(ctx, hipMemcpyAsync(level, d_lv, n, hipMemcpyDeviceToHost, ctx->stream));
-    FUS_OK(ctx, hipStreamSynchronize(ctx->stream));
+    hipLaunchKernelGGL(k_tat_levels, dim3(blocks), dim3(256), 0, ctx->stream, (const DevView *)ctx->d_views.p,
+                       (const apd_camera *)ctx->d_cams.p, ref, sl, dist_base, depth_base, q_k ? 1 : 0, cuts, d_pix, d_lv);
+    HIP_OK(ctx, hipGetLastError());
+    HIP_OK(ctx, hipMemcpyAsync(src_pix, d_pix, n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_OK(ctx, hipMemcpyAsync(level, d_lv, n, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_OK(ctx, hipStreamSynchronize(ctx->stream));
     return APD_OK;
 }
 

@@ -24,6 +24,7 @@
 
 #include "../../include/apd_hip.h"
 #include "apd_device.h"
+#include "apd_host.h"
 #include <rocprim/device/device_scan.hpp>
 
 using namespace apd;
@@ -4400,11 +4401,6 @@ __global__ __launch_bounds__(BLOCK) void k_result_epilogue(const float4 *__restr
 // =============================================================================================
 namespace {
 
-struct DevBuf {
-    void *p = nullptr;
-    size_t bytes = 0;
-};
-
 const char *g_global_err = "";
 std::string g_global_err_store;
 
@@ -4420,16 +4416,14 @@ enum TimingEv {
     TE_PREP_BEGIN = 0, TE_ANCHORS_END = 1, TE_PAIRS_END = 2, TE_JOIN_END = 3, TE_ITER0 = 4,  // iterations 0..7: 4..11
     TE_SWEEP_END = 12, TE_POST_END = 13, TE_LISTS_END = 14, TE_INIT_END = 15, TE_COUNT = 16
 };
-struct apd_ctx {
-    int device = 0;
-    hipStream_t stream = nullptr;
+struct apd_ctx : DevCtx {
+    apd_ctx() : DevCtx(nullptr) {}
     // side streams of the loop body: RANSACToGetFitPlane and k_gp_cost run beside the anchor
     // candidates' centre windows (none of them reads what another writes); the ctx stream joins them
     // before the kernels that read their outputs. ev_fork / ev_side: ordering only (no timing).
     hipStream_t side[2] = {nullptr, nullptr};
     hipEvent_t ev_fork = nullptr, ev_side[2] = {nullptr, nullptr};
     bool overlap = true;           // APD_NO_OVERLAP=1: the loop body on the ctx stream alone
-    std::string err;
     // buffers
     DevBuf imgs, quad, depth, views, cams, plane, cost, sel, sel2, vw, weak, conf, sa, amap, anchors, reliable, nearest,
         fit, curve, lists, rowcnt, rowoff, totals, near_off, dargs, evals, near_ring, near_g, wcand, lrs, wcur, arec, ga_stage,
@@ -4491,29 +4485,6 @@ struct apd_ctx {
     std::vector<hipEvent_t> prof_pool;  // recycled events (created once; no system-scope fence)
 };
 
-#define HIP_OK(ctx, call)                                                                          \
-    do {                                                                                           \
-        hipError_t e_ = (call);                                                                    \
-        if (e_ != hipSuccess) {                                                                    \
-            (ctx)->err = std::string(#call) + ": " + hipGetErrorString(e_);                        \
-            return APD_EDEVICE;                                                                    \
-        }                                                                                          \
-    } while (0)
-
-static int ensure(apd_ctx *ctx, DevBuf &b, size_t bytes) {
-    if (bytes == 0) bytes = 16;
-    if (b.bytes >= bytes) return APD_OK;
-    if (b.p) (void)hipFree(b.p);
-    b.p = nullptr;
-    b.bytes = 0;
-    if (hipMalloc(&b.p, bytes) != hipSuccess) {
-        ctx->err = "hipMalloc(" + std::to_string(bytes) + ") failed";
-        return APD_ENOMEM;
-    }
-    b.bytes = bytes;
-    return APD_OK;
-}
-
 static int check_launch(apd_ctx *ctx, const char *what) {
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
@@ -4570,14 +4541,14 @@ static int build_near_offsets(apd_ctx *ctx) {
     std::stable_sort(off.begin(), off.end(), [](const short2 &p, const short2 &q) {
         return p.x * p.x + p.y * p.y < q.x * q.x + q.y * q.y;  // stable: keeps x-major, y-minor order
     });
-    int st = ensure(ctx, ctx->near_off, off.size() * sizeof(short2));
+    int st = grow(ctx, ctx->near_off, off.size() * sizeof(short2));
     if (st) return st;
     HIP_OK(ctx, hipMemcpy(ctx->near_off.p, off.data(), off.size() * sizeof(short2), hipMemcpyHostToDevice));
     // ring_start[D] = first table index with d^2 >= D, D = 0 .. 20001
     std::vector<int> ring(20002, (int)off.size());
     for (int k = (int)off.size() - 1; k >= 0; --k) ring[off[k].x * off[k].x + off[k].y * off[k].y] = k;
     for (int D = 20000; D >= 0; --D) ring[D] = std::min(ring[D], ring[D + 1]);
-    if ((st = ensure(ctx, ctx->near_ring, ring.size() * sizeof(int)))) return st;
+    if ((st = grow(ctx, ctx->near_ring, ring.size() * sizeof(int)))) return st;
     HIP_OK(ctx, hipMemcpy(ctx->near_ring.p, ring.data(), ring.size() * sizeof(int), hipMemcpyHostToDevice));
     ctx->n_near = (int)off.size();
     return APD_OK;
@@ -4644,24 +4615,13 @@ int32_t apd_device_count(void) {
 }
 
 apd_ctx *apd_create(int32_t device) {
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) {
-        set_global_err("no HIP device visible");
-        return nullptr;
-    }
-    if (device < 0 || device >= n) {
-        set_global_err("device index out of range");
-        return nullptr;
-    }
-    if (hipSetDevice(device) != hipSuccess) {
-        set_global_err("hipSetDevice failed");
-        return nullptr;
-    }
-    apd_ctx *ctx = new apd_ctx();
-    ctx->device = device;
-    if (hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking) != hipSuccess) {
-        set_global_err("hipStreamCreate failed");
-        delete ctx;
+    OpenStep why;
+    apd_ctx *ctx = open_ctx<apd_ctx>(device, &why);
+    if (!ctx) {
+        set_global_err(why == OPEN_NO_DEVICE    ? "no HIP device visible"
+                       : why == OPEN_BAD_INDEX  ? "device index out of range"
+                       : why == OPEN_SET_DEVICE ? "hipSetDevice failed"
+                                                : "hipStreamCreate failed");
         return nullptr;
     }
     for (auto &e : ctx->ev) (void)hipEventCreateWithFlags(&e, hipEventDisableSystemFence);  // timing only
@@ -4748,14 +4708,6 @@ void apd_destroy(apd_ctx *ctx) {
     if (!ctx) return;
     (void)hipSetDevice(ctx->device);
     drain(ctx);
-    DevBuf *bufs[] = {&ctx->imgs, &ctx->quad, &ctx->depth, &ctx->views, &ctx->cams, &ctx->plane, &ctx->cost,
-                      &ctx->sel, &ctx->sel2, &ctx->vw, &ctx->weak, &ctx->conf, &ctx->sa, &ctx->amap, &ctx->anchors,
-                      &ctx->reliable, &ctx->nearest, &ctx->fit, &ctx->curve, &ctx->lists, &ctx->rowcnt,
-                      &ctx->rowoff, &ctx->totals, &ctx->near_off, &ctx->dargs, &ctx->evals, &ctx->near_ring, &ctx->near_g, &ctx->wcand, &ctx->arec, &ctx->ga_stage,
-                      &ctx->lrs, &ctx->wcur, &ctx->wlist, &ctx->gp_cb, &ctx->gp_cnt, &ctx->gp_cur, &ctx->gp_refs, &ctx->gp_ccnt,
-                      &ctx->gp_cbase, &ctx->gp_plist, &ctx->gp_pidx, &ctx->gp_pcost, &ctx->gp_tmp, &ctx->dpairs, &ctx->gp_cls};
-    for (DevBuf *b : bufs)
-        if (b->p) (void)hipFree(b->p);
     for (auto &e : ctx->ev) (void)hipEventDestroy(e);
     for (auto &pe : ctx->prof_ev) { (void)hipEventDestroy(pe.e0); (void)hipEventDestroy(pe.e1); }
     for (hipEvent_t e : ctx->prof_pool) (void)hipEventDestroy(e);
@@ -4763,17 +4715,16 @@ void apd_destroy(apd_ctx *ctx) {
     if (ctx->ev_fork) (void)hipEventDestroy(ctx->ev_fork);
     for (auto &e : ctx->ev_side) if (e) (void)hipEventDestroy(e);
     (void)hipStreamDestroy(ctx->stream);
-    delete ctx;
+    delete ctx;  // the buffers with it
 }
 
 const char *apd_last_error(const apd_ctx *ctx) { return ctx ? ctx->err.c_str() : g_global_err; }
 
-// ensure() for optional buffers: a failed allocation leaves no error behind (the caller falls back to
+// grow() for optional buffers: a failed allocation leaves no error behind (the caller falls back to
 // a slower exact path); the first few are reported on stderr, since a device store sized too greedily
 // by the caller shows up here first
 static bool try_ensure(apd_ctx *ctx, DevBuf &b, size_t bytes) {
-    if (ensure(ctx, b, bytes) == APD_OK) return true;
-    (void)hipGetLastError();
+    if (grow(ctx, b, bytes) == APD_OK) return true;
     ctx->err.clear();
     if (ctx->optional_fallbacks++ < 8)
         fprintf(stderr, "apd: optional device buffer of %zu bytes not allocated on device %d: its exact fallback path runs\n",
@@ -4806,24 +4757,24 @@ int32_t apd_set_problem(apd_ctx *ctx, const apd_problem *pb) {
     // Every input may be a host or a device pointer (hipMemcpyDefault): a caller that keeps a scan's
     // images and depth maps resident in HBM (scan_runner.py) hands device pointers over and nothing
     // crosses PCIe here.
-    if ((st = ensure(ctx, ctx->imgs, HW * NI * sizeof(float)))) return st;
-    if ((st = ensure(ctx, ctx->totals, 16 * sizeof(int)))) return st;
-    if ((st = ensure(ctx, ctx->plane, HW * sizeof(float4)))) return st;
-    if ((st = ensure(ctx, ctx->cost, HW * sizeof(float)))) return st;
-    if ((st = ensure(ctx, ctx->sel, HW * sizeof(uint32_t)))) return st;
-    if ((st = ensure(ctx, ctx->sel2, HW * sizeof(uint32_t)))) return st;
-    if ((st = ensure(ctx, ctx->vw, HW * N))) return st;
-    if ((st = ensure(ctx, ctx->weak, HW))) return st;
-    if ((st = ensure(ctx, ctx->conf, HW))) return st;
-    if ((st = ensure(ctx, ctx->sa, HW))) return st;
-    if ((st = ensure(ctx, ctx->lists, (HW + 8) * sizeof(int)))) return st;
-    if ((st = ensure(ctx, ctx->views, NI * sizeof(SrcView)))) return st;
-    if ((st = ensure(ctx, ctx->cams, NI * sizeof(Cam)))) return st;
+    if ((st = grow(ctx, ctx->imgs, HW * NI * sizeof(float)))) return st;
+    if ((st = grow(ctx, ctx->totals, 16 * sizeof(int)))) return st;
+    if ((st = grow(ctx, ctx->plane, HW * sizeof(float4)))) return st;
+    if ((st = grow(ctx, ctx->cost, HW * sizeof(float)))) return st;
+    if ((st = grow(ctx, ctx->sel, HW * sizeof(uint32_t)))) return st;
+    if ((st = grow(ctx, ctx->sel2, HW * sizeof(uint32_t)))) return st;
+    if ((st = grow(ctx, ctx->vw, HW * N))) return st;
+    if ((st = grow(ctx, ctx->weak, HW))) return st;
+    if ((st = grow(ctx, ctx->conf, HW))) return st;
+    if ((st = grow(ctx, ctx->sa, HW))) return st;
+    if ((st = grow(ctx, ctx->lists, (HW + 8) * sizeof(int)))) return st;
+    if ((st = grow(ctx, ctx->views, NI * sizeof(SrcView)))) return st;
+    if ((st = grow(ctx, ctx->cams, NI * sizeof(Cam)))) return st;
     const size_t units = std::max<size_t>((size_t)H, (size_t)(W + 3) / 4 * ((H + 3) / 4));  // any tile shape
-    if ((st = ensure(ctx, ctx->rowcnt, units * sizeof(int)))) return st;
-    if ((st = ensure(ctx, ctx->rowoff, units * sizeof(int)))) return st;
+    if ((st = grow(ctx, ctx->rowcnt, units * sizeof(int)))) return st;
+    if ((st = grow(ctx, ctx->rowoff, units * sizeof(int)))) return st;
     const bool need_depth = P.geom_consistency || P.use_APD;
-    if (need_depth && (st = ensure(ctx, ctx->depth, HW * NI * sizeof(float)))) return st;
+    if (need_depth && (st = grow(ctx, ctx->depth, HW * NI * sizeof(float)))) return st;
     for (int i = 0; i < NI; ++i) {
         if (!pb->images[i]) { ctx->err = "null image pointer"; return APD_EINVAL; }
         HIP_OK(ctx, hipMemcpyAsync((float *)ctx->imgs.p + HW * i, pb->images[i], HW * sizeof(float), hipMemcpyDefault, s));
@@ -4871,7 +4822,7 @@ int32_t apd_set_problem(apd_ctx *ctx, const apd_problem *pb) {
     const int max_conf = ctx->host_stat[2];
     const int sa_any = ctx->host_stat[3];
     const size_t qstride = tex_f16 ? (size_t)(W + 2) * (H + 1) : (size_t)(W + 1) * (H + 1);
-    if ((st = ensure(ctx, ctx->quad, qstride * N * (tex_f16 ? sizeof(uint32_t) : sizeof(float4))))) return st;
+    if ((st = grow(ctx, ctx->quad, qstride * N * (tex_f16 ? sizeof(uint32_t) : sizeof(float4))))) return st;
     std::vector<Cam> cams(NI);
     std::vector<SrcView> views(NI);
     for (int i = 0; i < NI; ++i) {
@@ -4890,18 +4841,18 @@ int32_t apd_set_problem(apd_ctx *ctx, const apd_problem *pb) {
     HIP_OK(ctx, hipMemsetAsync(ctx->sel.p, 0, HW * sizeof(uint32_t), s));
     ctx->weak_count = weak_count;
     if (P.use_APD) {
-        if ((st = ensure(ctx, ctx->amap, HW * sizeof(int)))) return st;
-        if ((st = ensure(ctx, ctx->anchors, (size_t)std::max(weak_count, 1) * 9 * sizeof(short2)))) return st;
-        if ((st = ensure(ctx, ctx->reliable, HW))) return st;
-        if ((st = ensure(ctx, ctx->nearest, HW * sizeof(short2)))) return st;
-        if ((st = ensure(ctx, ctx->fit, HW * sizeof(float4)))) return st;
+        if ((st = grow(ctx, ctx->amap, HW * sizeof(int)))) return st;
+        if ((st = grow(ctx, ctx->anchors, (size_t)std::max(weak_count, 1) * 9 * sizeof(short2)))) return st;
+        if ((st = grow(ctx, ctx->reliable, HW))) return st;
+        if ((st = grow(ctx, ctx->nearest, HW * sizeof(short2)))) return st;
+        if ((st = grow(ctx, ctx->fit, HW * sizeof(float4)))) return st;
         HIP_OK(ctx, hipMemsetAsync(ctx->reliable.p, 0, HW, s));
         HIP_OK(ctx, hipMemsetAsync(ctx->fit.p, 0, HW * sizeof(float4), s));
         if ((st = build_near_offsets(ctx))) return st;
         // per-level column distances for k_find_nearest_rows (confidence is an input here)
         ctx->near_levels = std::max(max_conf, 1) + 1;
         if (getenv("APD_NEAREST_RING") || (size_t)ctx->near_levels * HW > ((size_t)4 << 30)) ctx->near_levels = 0;
-        if (ctx->near_levels && (st = ensure(ctx, ctx->near_g, (size_t)ctx->near_levels * HW))) return st;
+        if (ctx->near_levels && (st = grow(ctx, ctx->near_g, (size_t)ctx->near_levels * HW))) return st;
     }
     // kernel arguments
     a.W = W; a.H = H; a.HW = (int)HW; a.N = N;
@@ -4953,10 +4904,10 @@ int32_t apd_set_problem(apd_ctx *ctx, const apd_problem *pb) {
     a.lr_geo = nullptr;
     a.wcur = nullptr;
     if (ctx->wcur_on) {  // the initial planes' costs per view (NCC-New for WEAK pixels), [N][H*W]
-        if ((st = ensure(ctx, ctx->wcur, HW * N * sizeof(float)))) return st;
+        if ((st = grow(ctx, ctx->wcur, HW * N * sizeof(float)))) return st;
         a.wcur = devptr<decltype(a.wcur)>(ctx->wcur.p);
     }
-    if ((st = ensure(ctx, ctx->dargs, sizeof(Args)))) return st;
+    if ((st = grow(ctx, ctx->dargs, sizeof(Args)))) return st;
     a.self = devptr<decltype(a.self)>(ctx->dargs.p);
     HIP_OK(ctx, hipMemcpyAsync(ctx->dargs.p, &a, sizeof(Args), hipMemcpyHostToDevice, s));
     // source images -> quad gather layout
@@ -4983,7 +4934,7 @@ int32_t apd_set_problem(apd_ctx *ctx, const apd_problem *pb) {
     }
     ctx->want_curve = pb->export_reliable_curve != 0;
     if (ctx->want_curve) {  // DepthToWeak cost curves (APD.cu:2188-2198, 2713-2724)
-        if ((st = ensure(ctx, ctx->curve, HW * 61 * sizeof(float)))) return st;
+        if ((st = grow(ctx, ctx->curve, HW * 61 * sizeof(float)))) return st;
         HIP_OK(ctx, hipMemsetAsync(ctx->curve.p, 0, HW * 61 * sizeof(float), s));
     }
     // DepthToWeak -> LocalRefine hand-over ([11][N][tile slots] fp32 NCC-Old, and as much again for
@@ -4997,18 +4948,11 @@ int32_t apd_set_problem(apd_ctx *ctx, const apd_problem *pb) {
         const int tw = ctx->dw_tile_w, th = VM_P / tw;
         const size_t slots = (size_t)(((W + tw - 1) / tw) * ((H + th - 1) / th)) * VM_P;
         const size_t need = (size_t)11 * N * slots * sizeof(float) * (P.geom_consistency ? 2 : 1);
-        if (ctx->lrs.p && ctx->lrs.bytes != need) {
-            (void)hipFree(ctx->lrs.p);
-            ctx->lrs.p = nullptr;
-            ctx->lrs.bytes = 0;
-        }
+        if (ctx->lrs.p && ctx->lrs.bytes != need) release(ctx, ctx->lrs);
         size_t free_b = 0, total_b = 0;
         const size_t spare = (size_t)4 << 30;
         if (!ctx->lrs.p && hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b > spare && need <= free_b - spare) {
-            if (ensure(ctx, ctx->lrs, need) != APD_OK) {  // not fatal: clear the allocation error
-                (void)hipGetLastError();
-                ctx->err.clear();
-            }
+            if (grow(ctx, ctx->lrs, need) != APD_OK) ctx->err.clear();  // not fatal
         }
         if (ctx->lrs.p) ctx->lrs_need = need;
     }
@@ -5357,14 +5301,14 @@ int32_t apd_stage_prepare(apd_ctx *ctx) {
         if (a.use_apd && nw > 0) {
             // the Weak sweep and the anchor candidates' kernels run once per iteration over the WEAK
             // pixels of both colours (tile order, dense 64-entry groups): see apd_stage_iteration
-            if ((st = ensure(ctx, ctx->wlist, (size_t)nw * sizeof(int)))) return st;
+            if ((st = grow(ctx, ctx->wlist, (size_t)nw * sizeof(int)))) return st;
             if ((st = build_tile_list(ctx, 1, 2, (int *)ctx->wlist.p, tot + 5, ctx->weak_quad))) return st;
         }
         if (a.use_apd && ctx->cand_pairs && nw > 0) {
             // the candidates' costs, by the dense list's groups (cand_at) or by WEAK index
             const size_t wc = (size_t)std::max(ctx->weak_count, 1);
             if (test_enomem_hook(ctx)) return APD_ENOMEM;  // (RandomInitialization is in flight on side stream 0)
-            if ((st = ensure(ctx, ctx->wcand, wcand_bytes(a.N, wc, nw)))) return st;
+            if ((st = grow(ctx, ctx->wcand, wcand_bytes(a.N, wc, nw)))) return st;
             (void)hipEventRecord(ctx->ev[TE_LISTS_END], s);
             // (the table's keys hold a pixel index below 2^25 and x below 2^15; else the sweep
             // evaluates the candidates itself)
@@ -5730,7 +5674,7 @@ int32_t apd_profile_reset(apd_ctx *ctx, int32_t enable) {
     ctx->prof = enable != 0;
     if (ctx->prof) {
         const size_t bytes = (size_t)APD_PROF_SLOTS * APD_PROF_SPREAD * sizeof(unsigned long long);
-        int st = ensure(ctx, ctx->evals, bytes);
+        int st = grow(ctx, ctx->evals, bytes);
         if (st) return st;
         HIP_OK(ctx, hipMemsetAsync(ctx->evals.p, 0, bytes, ctx->stream));
     }
@@ -5840,16 +5784,7 @@ int32_t apd_device_copy_peer(apd_ctx *dst_ctx, void *dst, apd_ctx *src_ctx, cons
 
 int32_t apd_device_bytes(apd_ctx *ctx, size_t *bytes) {
     if (!ctx || !bytes) return APD_EINVAL;
-    const DevBuf *bufs[] = {&ctx->imgs, &ctx->quad, &ctx->depth, &ctx->views, &ctx->cams, &ctx->plane, &ctx->cost,
-                            &ctx->sel, &ctx->sel2, &ctx->vw, &ctx->weak, &ctx->conf, &ctx->sa, &ctx->amap, &ctx->anchors,
-                            &ctx->reliable, &ctx->nearest, &ctx->fit, &ctx->curve, &ctx->lists, &ctx->rowcnt,
-                            &ctx->rowoff, &ctx->totals, &ctx->near_off, &ctx->dargs, &ctx->evals, &ctx->near_ring, &ctx->near_g,
-                            &ctx->wcand, &ctx->arec, &ctx->ga_stage, &ctx->lrs, &ctx->wcur, &ctx->wlist, &ctx->gp_cb, &ctx->gp_cnt,
-                            &ctx->gp_cur, &ctx->gp_refs, &ctx->gp_ccnt, &ctx->gp_cbase, &ctx->gp_plist, &ctx->gp_pidx,
-                            &ctx->gp_pcost, &ctx->gp_tmp, &ctx->dpairs, &ctx->gp_cls};
-    size_t t = 0;
-    for (const DevBuf *b : bufs) t += b->bytes;
-    *bytes = t;
+    *bytes = ctx->held;
     return APD_OK;
 }
 

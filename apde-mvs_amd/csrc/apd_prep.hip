@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "../../include/apd_prep.h"
+#include "apd_host.h"
 #include "apd_undistort.h"
 
 namespace {
@@ -297,66 +298,28 @@ void launch_undistort(const apd_ud::Warp &W, hipStream_t s) {
     hipLaunchKernelGGL(k_pr_undistort<M>, grid, dim3(UD_TILE_W, UD_TILE_H), 0, s, W);
 }
 
-struct Buf {
-    void *p = nullptr;
-    size_t bytes = 0;
-};
-
 inline int grid_for(int64_t n) { return (int)((n + BLOCK - 1) / BLOCK); }
 
 }  // namespace
 
-struct apd_prep_ctx {
-    int device = 0;
-    hipStream_t stream = nullptr;
+struct apd_prep_ctx : DevCtx {
+    apd_prep_ctx() : DevCtx("apd_prep") {}
     hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr, ev3 = nullptr;
-    std::string err;
     // model
-    Buf rot, trans, centres, xyz, obs_off, obs_point;
+    DevBuf rot, trans, centres, xyz, obs_off, obs_point;
     // tracks
-    Buf keys, keys_s, head_u, head_p, pos_u, pos_p, u_image, t_start, t_point, rec, rec_off, counts;
+    DevBuf keys, keys_s, head_u, head_p, pos_u, pos_p, u_image, t_start, t_point, rec, rec_off, counts;
     // pair counts and depth ranks
-    Buf m_shared, m_narrow, z_keys, z_sorted, frac, z_at;
-    Buf tmp;
+    DevBuf m_shared, m_narrow, z_keys, z_sorted, frac, z_at;
+    DevBuf tmp;
     // undistortion: the source and the warped image
-    Buf ud_src, ud_dst;
+    DevBuf ud_src, ud_dst;
     double ud_upload_ms = 0.0, ud_kernel_ms = 0.0, ud_download_ms = 0.0;
     bool has_model = false;
     int n_images = 0, n_points = 0, n_obs = 0, n_tracks = 0;
     uint64_t total = 0;
     double tracks_ms = 0.0, pairs_ms = 0.0, records_ms = 0.0, ranks_ms = 0.0;
 };
-
-#define PR_OK(ctx, call)                                                                           \
-    do {                                                                                           \
-        hipError_t e_ = (call);                                                                    \
-        if (e_ != hipSuccess) {                                                                    \
-            (ctx)->err = std::string(#call) + ": " + hipGetErrorString(e_);                        \
-            return APD_EDEVICE;                                                                    \
-        }                                                                                          \
-    } while (0)
-
-static int grow(apd_prep_ctx *ctx, Buf &b, size_t bytes) {
-    if (b.bytes >= bytes && b.p) return APD_OK;
-    if (b.p) (void)hipFree(b.p);
-    b.p = nullptr;
-    b.bytes = 0;
-    if (bytes == 0) bytes = 16;
-    if (hipMalloc(&b.p, bytes) != hipSuccess) {
-        b.p = nullptr;
-        ctx->err = "apd_prep: device allocation of " + std::to_string(bytes) + " bytes failed";
-        return APD_ENOMEM;
-    }
-    b.bytes = bytes;
-    return APD_OK;
-}
-
-static int elapsed(apd_prep_ctx *ctx, double &ms) {
-    float f = 0.0f;
-    PR_OK(ctx, hipEventElapsedTime(&f, ctx->ev0, ctx->ev1));
-    ms = (double)f;
-    return APD_OK;
-}
 
 static int fail(apd_prep_ctx *ctx, const std::string &msg) {
     ctx->err = msg;
@@ -372,23 +335,19 @@ static bool all_finite(const double *p, size_t n) {
 template <class T>
 static int scan_u(apd_prep_ctx *ctx, const T *in, T *out, size_t n) {
     size_t tb = 0;
-    PR_OK(ctx, rocprim::exclusive_scan(nullptr, tb, in, out, T(0), n, rocprim::plus<T>(), ctx->stream));
+    HIP_OK(ctx, rocprim::exclusive_scan(nullptr, tb, in, out, T(0), n, rocprim::plus<T>(), ctx->stream));
     int st = grow(ctx, ctx->tmp, tb);
     if (st) return st;
-    PR_OK(ctx, rocprim::exclusive_scan(ctx->tmp.p, tb, in, out, T(0), n, rocprim::plus<T>(), ctx->stream));
+    HIP_OK(ctx, rocprim::exclusive_scan(ctx->tmp.p, tb, in, out, T(0), n, rocprim::plus<T>(), ctx->stream));
     return APD_OK;
 }
 
 extern "C" {
 
 apd_prep_ctx *apd_prep_create(int32_t device) {
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || device < 0 || device >= n) return nullptr;
-    if (hipSetDevice(device) != hipSuccess) return nullptr;
-    auto *ctx = new apd_prep_ctx();
-    ctx->device = device;
-    if (hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking) != hipSuccess ||
-        hipEventCreate(&ctx->ev0) != hipSuccess || hipEventCreate(&ctx->ev1) != hipSuccess ||
+    auto *ctx = open_ctx<apd_prep_ctx>(device);
+    if (!ctx) return nullptr;
+    if (hipEventCreate(&ctx->ev0) != hipSuccess || hipEventCreate(&ctx->ev1) != hipSuccess ||
         hipEventCreate(&ctx->ev2) != hipSuccess || hipEventCreate(&ctx->ev3) != hipSuccess) {
         apd_prep_destroy(ctx);
         return nullptr;
@@ -399,17 +358,12 @@ apd_prep_ctx *apd_prep_create(int32_t device) {
 void apd_prep_destroy(apd_prep_ctx *ctx) {
     if (!ctx) return;
     (void)hipSetDevice(ctx->device);
-    for (Buf *b : {&ctx->rot, &ctx->trans, &ctx->centres, &ctx->xyz, &ctx->obs_off, &ctx->obs_point, &ctx->keys,
-                   &ctx->keys_s, &ctx->head_u, &ctx->head_p, &ctx->pos_u, &ctx->pos_p, &ctx->u_image, &ctx->t_start,
-                   &ctx->t_point, &ctx->rec, &ctx->rec_off, &ctx->counts, &ctx->m_shared, &ctx->m_narrow, &ctx->z_keys,
-                   &ctx->z_sorted, &ctx->frac, &ctx->z_at, &ctx->tmp, &ctx->ud_src, &ctx->ud_dst})
-        if (b->p) (void)hipFree(b->p);
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
     if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
     if (ctx->ev2) (void)hipEventDestroy(ctx->ev2);
     if (ctx->ev3) (void)hipEventDestroy(ctx->ev3);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
-    delete ctx;
+    delete ctx;  // the buffers with it
 }
 
 const char *apd_prep_last_error(const apd_prep_ctx *ctx) {
@@ -439,7 +393,7 @@ int32_t apd_prep_set_model(apd_prep_ctx *ctx, int32_t n_images, const double *ro
         !all_finite(centres, 3 * (size_t)n_images) || !all_finite(xyz, 3 * (size_t)n_points))
         return fail(ctx, std::string(W) + "a non-finite value");
 
-    PR_OK(ctx, hipSetDevice(ctx->device));
+    HIP_OK(ctx, hipSetDevice(ctx->device));
     ctx->has_model = false;
     ctx->tracks_ms = 0.0;
     const int n = (int)n_obs;
@@ -456,33 +410,33 @@ int32_t apd_prep_set_model(apd_prep_ctx *ctx, int32_t n_images, const double *ro
         (st = grow(ctx, ctx->rec_off, 8 * cap)) || (st = grow(ctx, ctx->counts, 16)))
         return st;
     hipStream_t s = ctx->stream;
-    PR_OK(ctx, hipMemcpyAsync(ctx->rot.p, rot, 72 * (size_t)n_images, hipMemcpyHostToDevice, s));
-    PR_OK(ctx, hipMemcpyAsync(ctx->trans.p, trans, 24 * (size_t)n_images, hipMemcpyHostToDevice, s));
-    PR_OK(ctx, hipMemcpyAsync(ctx->centres.p, centres, 24 * (size_t)n_images, hipMemcpyHostToDevice, s));
-    PR_OK(ctx, hipMemcpyAsync(ctx->obs_off.p, obs_offset, 8 * ((size_t)n_images + 1), hipMemcpyHostToDevice, s));
-    if (n_points) PR_OK(ctx, hipMemcpyAsync(ctx->xyz.p, xyz, 24 * (size_t)n_points, hipMemcpyHostToDevice, s));
-    if (n) PR_OK(ctx, hipMemcpyAsync(ctx->obs_point.p, obs_point, 4 * (size_t)n, hipMemcpyHostToDevice, s));
+    HIP_OK(ctx, hipMemcpyAsync(ctx->rot.p, rot, 72 * (size_t)n_images, hipMemcpyHostToDevice, s));
+    HIP_OK(ctx, hipMemcpyAsync(ctx->trans.p, trans, 24 * (size_t)n_images, hipMemcpyHostToDevice, s));
+    HIP_OK(ctx, hipMemcpyAsync(ctx->centres.p, centres, 24 * (size_t)n_images, hipMemcpyHostToDevice, s));
+    HIP_OK(ctx, hipMemcpyAsync(ctx->obs_off.p, obs_offset, 8 * ((size_t)n_images + 1), hipMemcpyHostToDevice, s));
+    if (n_points) HIP_OK(ctx, hipMemcpyAsync(ctx->xyz.p, xyz, 24 * (size_t)n_points, hipMemcpyHostToDevice, s));
+    if (n) HIP_OK(ctx, hipMemcpyAsync(ctx->obs_point.p, obs_point, 4 * (size_t)n, hipMemcpyHostToDevice, s));
     ctx->n_images = n_images;
     ctx->n_points = (int)n_points;
     ctx->n_obs = n;
     ctx->n_tracks = 0;
     ctx->total = 0;
     if (n > 0) {
-        PR_OK(ctx, hipEventRecord(ctx->ev0, s));
+        HIP_OK(ctx, hipEventRecord(ctx->ev0, s));
         hipLaunchKernelGGL(k_pr_keys, dim3(grid_for(n)), dim3(BLOCK), 0, s, (const int64_t *)ctx->obs_off.p, n_images,
                            (const int *)ctx->obs_point.p, n, (uint64_t *)ctx->keys.p);
-        PR_OK(ctx, hipGetLastError());
+        HIP_OK(ctx, hipGetLastError());
         unsigned end_bit = 33;  // image bits (32, the low word) + the bits of the largest point index
         while (end_bit < 64 && ((uint64_t)n_points >> (end_bit - 32)) != 0) ++end_bit;
         size_t tb = 0;
-        PR_OK(ctx, rocprim::radix_sort_keys(nullptr, tb, (uint64_t *)ctx->keys.p, (uint64_t *)ctx->keys_s.p, (size_t)n,
+        HIP_OK(ctx, rocprim::radix_sort_keys(nullptr, tb, (uint64_t *)ctx->keys.p, (uint64_t *)ctx->keys_s.p, (size_t)n,
                                             0, end_bit, s));
         if ((st = grow(ctx, ctx->tmp, tb))) return st;
-        PR_OK(ctx, rocprim::radix_sort_keys(ctx->tmp.p, tb, (uint64_t *)ctx->keys.p, (uint64_t *)ctx->keys_s.p,
+        HIP_OK(ctx, rocprim::radix_sort_keys(ctx->tmp.p, tb, (uint64_t *)ctx->keys.p, (uint64_t *)ctx->keys_s.p,
                                             (size_t)n, 0, end_bit, s));
         hipLaunchKernelGGL(k_pr_heads, dim3(grid_for(n)), dim3(BLOCK), 0, s, (const uint64_t *)ctx->keys_s.p, n,
                            (uint32_t *)ctx->head_u.p, (uint32_t *)ctx->head_p.p);
-        PR_OK(ctx, hipGetLastError());
+        HIP_OK(ctx, hipGetLastError());
         if ((st = scan_u<uint32_t>(ctx, (const uint32_t *)ctx->head_u.p, (uint32_t *)ctx->pos_u.p, (size_t)n)) ||
             (st = scan_u<uint32_t>(ctx, (const uint32_t *)ctx->head_p.p, (uint32_t *)ctx->pos_p.p, (size_t)n)))
             return st;
@@ -490,10 +444,10 @@ int32_t apd_prep_set_model(apd_prep_ctx *ctx, int32_t n_images, const double *ro
                            (const uint32_t *)ctx->head_u.p, (const uint32_t *)ctx->head_p.p,
                            (const uint32_t *)ctx->pos_u.p, (const uint32_t *)ctx->pos_p.p, (uint32_t *)ctx->u_image.p,
                            (uint32_t *)ctx->t_start.p, (uint32_t *)ctx->t_point.p, (uint32_t *)ctx->counts.p);
-        PR_OK(ctx, hipGetLastError());
+        HIP_OK(ctx, hipGetLastError());
         uint32_t counts[2] = {0, 0};
-        PR_OK(ctx, hipMemcpyAsync(counts, ctx->counts.p, 8, hipMemcpyDeviceToHost, s));
-        PR_OK(ctx, hipStreamSynchronize(s));
+        HIP_OK(ctx, hipMemcpyAsync(counts, ctx->counts.p, 8, hipMemcpyDeviceToHost, s));
+        HIP_OK(ctx, hipStreamSynchronize(s));
         const int T = (int)counts[1];
         if (T < 1 || T > n || counts[0] < (uint32_t)T || counts[0] > (uint32_t)n) {
             ctx->err = std::string(W) + "inconsistent track counts";
@@ -501,18 +455,18 @@ int32_t apd_prep_set_model(apd_prep_ctx *ctx, int32_t n_images, const double *ro
         }
         hipLaunchKernelGGL(k_pr_track_records, dim3(grid_for((int64_t)T + 1)), dim3(BLOCK), 0, s,
                            (const uint32_t *)ctx->t_start.p, T, (uint64_t *)ctx->rec.p);
-        PR_OK(ctx, hipGetLastError());
+        HIP_OK(ctx, hipGetLastError());
         if ((st = scan_u<uint64_t>(ctx, (const uint64_t *)ctx->rec.p, (uint64_t *)ctx->rec_off.p, (size_t)T + 1)))
             return st;
         uint64_t total = 0;
-        PR_OK(ctx, hipMemcpyAsync(&total, (uint64_t *)ctx->rec_off.p + T, 8, hipMemcpyDeviceToHost, s));
-        PR_OK(ctx, hipEventRecord(ctx->ev1, s));
-        PR_OK(ctx, hipStreamSynchronize(s));
-        if ((st = elapsed(ctx, ctx->tracks_ms))) return st;
+        HIP_OK(ctx, hipMemcpyAsync(&total, (uint64_t *)ctx->rec_off.p + T, 8, hipMemcpyDeviceToHost, s));
+        HIP_OK(ctx, hipEventRecord(ctx->ev1, s));
+        HIP_OK(ctx, hipStreamSynchronize(s));
+        if ((st = event_ms(ctx, ctx->ev0, ctx->ev1, ctx->tracks_ms))) return st;
         ctx->n_tracks = T;
         ctx->total = total;
     } else {
-        PR_OK(ctx, hipStreamSynchronize(s));
+        HIP_OK(ctx, hipStreamSynchronize(s));
     }
     ctx->has_model = true;
     return APD_OK;
@@ -529,15 +483,15 @@ int32_t apd_prep_pair_counts(apd_prep_ctx *ctx, double q_gate, int32_t atomics, 
     if (q_gate != q_gate) return fail(ctx, "apd_prep_pair_counts: q_gate is NaN");
     if (atomics < APD_PREP_ATOMICS_DEFAULT || atomics > APD_PREP_ATOMICS_LDS)
         return fail(ctx, "apd_prep_pair_counts: unknown atomics mode");
-    PR_OK(ctx, hipSetDevice(ctx->device));
+    HIP_OK(ctx, hipSetDevice(ctx->device));
     const int n = ctx->n_images;
     const size_t mbytes = 4 * (size_t)n * (size_t)n;
     int st;
     if ((st = grow(ctx, ctx->m_shared, mbytes)) || (st = grow(ctx, ctx->m_narrow, mbytes))) return st;
     hipStream_t s = ctx->stream;
-    PR_OK(ctx, hipEventRecord(ctx->ev0, s));
-    PR_OK(ctx, hipMemsetAsync(ctx->m_shared.p, 0, mbytes, s));
-    PR_OK(ctx, hipMemsetAsync(ctx->m_narrow.p, 0, mbytes, s));
+    HIP_OK(ctx, hipEventRecord(ctx->ev0, s));
+    HIP_OK(ctx, hipMemsetAsync(ctx->m_shared.p, 0, mbytes, s));
+    HIP_OK(ctx, hipMemsetAsync(ctx->m_narrow.p, 0, mbytes, s));
     if (ctx->total > 0) {
         PairArgs A;
         A.rec_off = (const uint64_t *)ctx->rec_off.p;
@@ -554,7 +508,7 @@ int32_t apd_prep_pair_counts(apd_prep_ctx *ctx, double q_gate, int32_t atomics, 
         A.n_images = n;
         const uint64_t tiles = (ctx->total + TILE - 1) / TILE;
         const int grid = (int)std::min<uint64_t>(tiles, PAIR_GRID);
-        PR_OK(ctx, hipEventRecord(ctx->ev2, s));
+        HIP_OK(ctx, hipEventRecord(ctx->ev2, s));
         // Default: aggregate in LDS when the image pairs are hot on average. A tile of TILE records
         // then holds few distinct pairs and one global atomic stands for many records (2.4x at 40
         // images with 2 000 records per pair); with many images or very long tracks nearly every
@@ -567,23 +521,19 @@ int32_t apd_prep_pair_counts(apd_prep_ctx *ctx, double q_gate, int32_t atomics, 
             hipLaunchKernelGGL(k_pr_pairs<false>, dim3(grid), dim3(BLOCK), 0, s, A);
         else
             hipLaunchKernelGGL(k_pr_pairs<true>, dim3(grid), dim3(BLOCK), 0, s, A);
-        PR_OK(ctx, hipGetLastError());
-        PR_OK(ctx, hipEventRecord(ctx->ev3, s));
+        HIP_OK(ctx, hipGetLastError());
+        HIP_OK(ctx, hipEventRecord(ctx->ev3, s));
         hipLaunchKernelGGL(k_pr_mirror, dim3(grid_for((int64_t)n * n)), dim3(BLOCK), 0, s, (uint32_t *)ctx->m_shared.p,
                            (uint32_t *)ctx->m_narrow.p, n);
-        PR_OK(ctx, hipGetLastError());
+        HIP_OK(ctx, hipGetLastError());
     }
-    PR_OK(ctx, hipEventRecord(ctx->ev1, s));
-    PR_OK(ctx, hipMemcpyAsync(shared, ctx->m_shared.p, mbytes, hipMemcpyDefault, s));
-    if (narrow) PR_OK(ctx, hipMemcpyAsync(narrow, ctx->m_narrow.p, mbytes, hipMemcpyDefault, s));
-    PR_OK(ctx, hipStreamSynchronize(s));
-    if ((st = elapsed(ctx, ctx->pairs_ms))) return st;
+    HIP_OK(ctx, hipEventRecord(ctx->ev1, s));
+    HIP_OK(ctx, hipMemcpyAsync(shared, ctx->m_shared.p, mbytes, hipMemcpyDefault, s));
+    if (narrow) HIP_OK(ctx, hipMemcpyAsync(narrow, ctx->m_narrow.p, mbytes, hipMemcpyDefault, s));
+    HIP_OK(ctx, hipStreamSynchronize(s));
+    if ((st = event_ms(ctx, ctx->ev0, ctx->ev1, ctx->pairs_ms))) return st;
     ctx->records_ms = 0.0;
-    if (ctx->total > 0) {
-        float f = 0.0f;
-        PR_OK(ctx, hipEventElapsedTime(&f, ctx->ev2, ctx->ev3));
-        ctx->records_ms = (double)f;
-    }
+    if (ctx->total > 0 && (st = event_ms(ctx, ctx->ev2, ctx->ev3, ctx->records_ms))) return st;
     if (n_records) *n_records = ctx->total;
     return APD_OK;
 }
@@ -597,11 +547,11 @@ int32_t apd_prep_depth_ranks(apd_prep_ctx *ctx, int32_t num_fractions, const dou
     }
     if (num_fractions < 1 || num_fractions > 64) return fail(ctx, "apd_prep_depth_ranks: num_fractions outside 1..64");
     if (!fractions || !z_at) return fail(ctx, "apd_prep_depth_ranks: NULL fractions or z_at");
-    PR_OK(ctx, hipSetDevice(ctx->device));
+    HIP_OK(ctx, hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
     double hf[64];
-    PR_OK(ctx, hipMemcpyAsync(hf, fractions, 8 * (size_t)num_fractions, hipMemcpyDefault, s));
-    PR_OK(ctx, hipStreamSynchronize(s));
+    HIP_OK(ctx, hipMemcpyAsync(hf, fractions, 8 * (size_t)num_fractions, hipMemcpyDefault, s));
+    HIP_OK(ctx, hipStreamSynchronize(s));
     for (int k = 0; k < num_fractions; ++k)
         if (!(hf[k] >= 0.0 && hf[k] < 1.0)) return fail(ctx, "apd_prep_depth_ranks: a fraction outside [0, 1)");
     const int n = ctx->n_obs, ni = ctx->n_images;
@@ -610,33 +560,33 @@ int32_t apd_prep_depth_ranks(apd_prep_ctx *ctx, int32_t num_fractions, const dou
     if ((st = grow(ctx, ctx->z_keys, 8 * cap)) || (st = grow(ctx, ctx->z_sorted, 8 * cap)) ||
         (st = grow(ctx, ctx->frac, 8 * 64)) || (st = grow(ctx, ctx->z_at, 8 * out_n)))
         return st;
-    PR_OK(ctx, hipMemcpyAsync(ctx->frac.p, hf, 8 * (size_t)num_fractions, hipMemcpyHostToDevice, s));
-    PR_OK(ctx, hipEventRecord(ctx->ev0, s));
+    HIP_OK(ctx, hipMemcpyAsync(ctx->frac.p, hf, 8 * (size_t)num_fractions, hipMemcpyHostToDevice, s));
+    HIP_OK(ctx, hipEventRecord(ctx->ev0, s));
     const int64_t *off = (const int64_t *)ctx->obs_off.p;
     if (n > 0) {
         hipLaunchKernelGGL(k_pr_depth_keys, dim3(grid_for(n)), dim3(BLOCK), 0, s, off, ni, (const int *)ctx->obs_point.p,
                            n, (const double *)ctx->rot.p, (const double *)ctx->trans.p, (const double *)ctx->xyz.p,
                            (uint64_t *)ctx->z_keys.p);
-        PR_OK(ctx, hipGetLastError());
+        HIP_OK(ctx, hipGetLastError());
         size_t tb = 0;
-        PR_OK(ctx, rocprim::segmented_radix_sort_keys(nullptr, tb, (uint64_t *)ctx->z_keys.p, (uint64_t *)ctx->z_sorted.p,
+        HIP_OK(ctx, rocprim::segmented_radix_sort_keys(nullptr, tb, (uint64_t *)ctx->z_keys.p, (uint64_t *)ctx->z_sorted.p,
                                                       (unsigned)n, (unsigned)ni, off, off + 1, 0, 64, s));
         if ((st = grow(ctx, ctx->tmp, tb))) return st;
-        PR_OK(ctx, rocprim::segmented_radix_sort_keys(ctx->tmp.p, tb, (uint64_t *)ctx->z_keys.p,
+        HIP_OK(ctx, rocprim::segmented_radix_sort_keys(ctx->tmp.p, tb, (uint64_t *)ctx->z_keys.p,
                                                       (uint64_t *)ctx->z_sorted.p, (unsigned)n, (unsigned)ni, off,
                                                       off + 1, 0, 64, s));
     }
     hipLaunchKernelGGL(k_pr_pick, dim3(grid_for((int64_t)out_n)), dim3(BLOCK), 0, s, off, ni,
                        (const uint64_t *)ctx->z_sorted.p, (int)num_fractions, (const double *)ctx->frac.p,
                        (double *)ctx->z_at.p);
-    PR_OK(ctx, hipGetLastError());
-    PR_OK(ctx, hipEventRecord(ctx->ev1, s));
-    PR_OK(ctx, hipMemcpyAsync(z_at, ctx->z_at.p, 8 * out_n, hipMemcpyDefault, s));
-    PR_OK(ctx, hipStreamSynchronize(s));
-    if ((st = elapsed(ctx, ctx->ranks_ms))) return st;
+    HIP_OK(ctx, hipGetLastError());
+    HIP_OK(ctx, hipEventRecord(ctx->ev1, s));
+    HIP_OK(ctx, hipMemcpyAsync(z_at, ctx->z_at.p, 8 * out_n, hipMemcpyDefault, s));
+    HIP_OK(ctx, hipStreamSynchronize(s));
+    if ((st = event_ms(ctx, ctx->ev0, ctx->ev1, ctx->ranks_ms))) return st;
     if (n_obs_out) {
         std::vector<int64_t> ho((size_t)ni + 1);
-        PR_OK(ctx, hipMemcpy(ho.data(), ctx->obs_off.p, 8 * ((size_t)ni + 1), hipMemcpyDeviceToHost));
+        HIP_OK(ctx, hipMemcpy(ho.data(), ctx->obs_off.p, 8 * ((size_t)ni + 1), hipMemcpyDeviceToHost));
         for (int i = 0; i < ni; ++i) n_obs_out[i] = ho[i + 1] - ho[i];
     }
     return APD_OK;
@@ -658,7 +608,7 @@ int32_t apd_prep_undistort_bgr8(apd_prep_ctx *ctx, int32_t model_id, const doubl
     if (!ctx) return APD_EINVAL;
     if (const char *what = apd_ud::check_warp(model_id, params, n_params, src_w, src_h, src, out_K, out_w, out_h, dst))
         return fail(ctx, std::string("apd_prep_undistort_bgr8: ") + what);
-    PR_OK(ctx, hipSetDevice(ctx->device));
+    HIP_OK(ctx, hipSetDevice(ctx->device));
     const size_t src_bytes = 3 * (size_t)src_w * (size_t)src_h, dst_bytes = 3 * (size_t)out_w * (size_t)out_h;
     int st;
     if ((st = grow(ctx, ctx->ud_src, src_bytes)) || (st = grow(ctx, ctx->ud_dst, dst_bytes))) return st;
@@ -666,9 +616,9 @@ int32_t apd_prep_undistort_bgr8(apd_prep_ctx *ctx, int32_t model_id, const doubl
     apd_ud::fill_warp(W, params, n_params, src_w, src_h, (const uint8_t *)ctx->ud_src.p, out_K, out_w, out_h,
                       (uint8_t *)ctx->ud_dst.p);
     hipStream_t s = ctx->stream;
-    PR_OK(ctx, hipEventRecord(ctx->ev0, s));
-    PR_OK(ctx, hipMemcpyAsync(ctx->ud_src.p, src, src_bytes, hipMemcpyDefault, s));
-    PR_OK(ctx, hipEventRecord(ctx->ev2, s));
+    HIP_OK(ctx, hipEventRecord(ctx->ev0, s));
+    HIP_OK(ctx, hipMemcpyAsync(ctx->ud_src.p, src, src_bytes, hipMemcpyDefault, s));
+    HIP_OK(ctx, hipEventRecord(ctx->ev2, s));
     switch (model_id) {
         case apd_ud::SIMPLE_PINHOLE: launch_undistort<apd_ud::SIMPLE_PINHOLE>(W, s); break;
         case apd_ud::PINHOLE: launch_undistort<apd_ud::PINHOLE>(W, s); break;
@@ -681,19 +631,15 @@ int32_t apd_prep_undistort_bgr8(apd_prep_ctx *ctx, int32_t model_id, const doubl
         case apd_ud::RADIAL_FISHEYE: launch_undistort<apd_ud::RADIAL_FISHEYE>(W, s); break;
         default: launch_undistort<apd_ud::THIN_PRISM_FISHEYE>(W, s); break;
     }
-    PR_OK(ctx, hipGetLastError());
-    PR_OK(ctx, hipEventRecord(ctx->ev3, s));
-    PR_OK(ctx, hipMemcpyAsync(dst, ctx->ud_dst.p, dst_bytes, hipMemcpyDefault, s));
-    PR_OK(ctx, hipEventRecord(ctx->ev1, s));
-    PR_OK(ctx, hipStreamSynchronize(s));
-    float up = 0.0f, ke = 0.0f, down = 0.0f;
-    PR_OK(ctx, hipEventElapsedTime(&up, ctx->ev0, ctx->ev2));
-    PR_OK(ctx, hipEventElapsedTime(&ke, ctx->ev2, ctx->ev3));
-    PR_OK(ctx, hipEventElapsedTime(&down, ctx->ev3, ctx->ev1));
-    ctx->ud_upload_ms = (double)up;
-    ctx->ud_kernel_ms = (double)ke;
-    ctx->ud_download_ms = (double)down;
-    return APD_OK;
+    HIP_OK(ctx, hipGetLastError());
+    HIP_OK(ctx, hipEventRecord(ctx->ev3, s));
+    HIP_OK(ctx, hipMemcpyAsync(dst, ctx->ud_dst.p, dst_bytes, hipMemcpyDefault, s));
+    HIP_OK(ctx, hipEventRecord(ctx->ev1, s));
+    HIP_OK(ctx, hipStreamSynchronize(s));
+    if ((st = event_ms(ctx, ctx->ev0, ctx->ev2, ctx->ud_upload_ms)) ||
+        (st = event_ms(ctx, ctx->ev2, ctx->ev3, ctx->ud_kernel_ms)))
+        return st;
+    return event_ms(ctx, ctx->ev3, ctx->ev1, ctx->ud_download_ms);
 }
 
 int32_t apd_prep_get_undistort_timing(apd_prep_ctx *ctx, double *upload_ms, double *kernel_ms, double *download_ms) {

@@ -28,6 +28,7 @@
 #include <vector>
 
 #include "../../include/apd_seg.h"
+#include "apd_host.h"
 #include "apd_seg.h"
 
 namespace {
@@ -238,52 +239,20 @@ __global__ void __launch_bounds__(BLOCK) k_seg_relabel(const int *roots, int64_t
     labels[i] = r >= 0 ? label_of(t_root, t_label, table.n, r) : (uint8_t)0;
 }
 
-struct Buf {
-    void *p = nullptr;
-    size_t bytes = 0;
-};
-
 inline unsigned blocks_for(int64_t n) { return (unsigned)((n + BLOCK - 1) / BLOCK); }
 
 constexpr int NUM_EVENTS = APD_SEG_NUM_TIMES + 1;
 
 }  // namespace
 
-struct apd_seg_ctx {
-    int device = 0;
-    hipStream_t stream = nullptr;
+struct apd_seg_ctx : DevCtx {
+    apd_seg_ctx() : DevCtx("apd_seg") {}
     hipEvent_t ev[NUM_EVENTS] = {};
-    std::string err;
-    Buf src, work, smooth, flat, parent, roots, area, keys, keys_sorted, labels, tmp;
+    DevBuf src, work, smooth, flat, parent, roots, area, keys, keys_sorted, labels, tmp;
     int last = 0;  // 0: no call yet, 1: apd_seg_label_mask, 2: apd_seg_flat_zones_bgr8
     int W = 0, H = 0;
     double ms[APD_SEG_NUM_TIMES] = {};
 };
-
-#define SG_OK(ctx, call)                                                                           \
-    do {                                                                                           \
-        hipError_t e_ = (call);                                                                    \
-        if (e_ != hipSuccess) {                                                                    \
-            (ctx)->err = std::string(#call) + ": " + hipGetErrorString(e_);                        \
-            return APD_EDEVICE;                                                                    \
-        }                                                                                          \
-    } while (0)
-
-static int grow(apd_seg_ctx *ctx, Buf &b, size_t bytes) {
-    if (b.bytes >= bytes && b.p) return APD_OK;
-    if (b.p) (void)hipFree(b.p);
-    b.p = nullptr;
-    b.bytes = 0;
-    if (bytes == 0) bytes = 16;
-    if (hipMalloc(&b.p, bytes) != hipSuccess) {
-        b.p = nullptr;
-        (void)hipGetLastError();
-        ctx->err = "apd_seg: device allocation of " + std::to_string(bytes) + " bytes failed";
-        return APD_ENOMEM;
-    }
-    b.bytes = bytes;
-    return APD_OK;
-}
 
 static int fail(apd_seg_ctx *ctx, const std::string &msg) {
     ctx->err = msg;
@@ -299,43 +268,37 @@ static int run_components(apd_seg_ctx *ctx, int W, int H) {
         return st;
     const int ntx = ceil_div(W, TW), nty = ceil_div(H, TH);
     const dim3 tiles((unsigned)ntx, (unsigned)nty);
-    SG_OK(ctx, hipEventRecord(ctx->ev[3], s));
+    HIP_OK(ctx, hipEventRecord(ctx->ev[3], s));
     hipLaunchKernelGGL(k_seg_ccl_tile, tiles, dim3(BLOCK), 0, s, (const uint8_t *)ctx->flat.p, W, H, (int *)ctx->parent.p);
-    SG_OK(ctx, hipGetLastError());
-    SG_OK(ctx, hipEventRecord(ctx->ev[4], s));
+    HIP_OK(ctx, hipGetLastError());
+    HIP_OK(ctx, hipEventRecord(ctx->ev[4], s));
     const int64_t n_vertical = (int64_t)(ntx - 1) * H, n_pairs = n_vertical + (int64_t)(nty - 1) * W;
     if (n_pairs > 0) {
         hipLaunchKernelGGL(k_seg_ccl_merge, dim3(blocks_for(n_pairs)), dim3(BLOCK), 0, s, (int *)ctx->parent.p, W, H,
                            n_vertical, n_pairs);
-        SG_OK(ctx, hipGetLastError());
+        HIP_OK(ctx, hipGetLastError());
     }
-    SG_OK(ctx, hipEventRecord(ctx->ev[5], s));
-    SG_OK(ctx, hipMemsetAsync(ctx->area.p, 0, N * 4, s));
+    HIP_OK(ctx, hipEventRecord(ctx->ev[5], s));
+    HIP_OK(ctx, hipMemsetAsync(ctx->area.p, 0, N * 4, s));
     hipLaunchKernelGGL(k_seg_flatten_area, tiles, dim3(BLOCK), 0, s, (const int *)ctx->parent.p, W, H, (int *)ctx->roots.p,
                        (int *)ctx->area.p);
-    SG_OK(ctx, hipGetLastError());
-    SG_OK(ctx, hipEventRecord(ctx->ev[6], s));
+    HIP_OK(ctx, hipGetLastError());
+    HIP_OK(ctx, hipEventRecord(ctx->ev[6], s));
     return APD_OK;
 }
 
 static int read_times(apd_seg_ctx *ctx) {
-    for (int k = 0; k < APD_SEG_NUM_TIMES; ++k) {
-        float f = 0.0f;
-        SG_OK(ctx, hipEventElapsedTime(&f, ctx->ev[k], ctx->ev[k + 1]));
-        ctx->ms[k] = (double)f;
-    }
-    return APD_OK;
+    int st = APD_OK;
+    for (int k = 0; !st && k < APD_SEG_NUM_TIMES; ++k) st = event_ms(ctx, ctx->ev[k], ctx->ev[k + 1], ctx->ms[k]);
+    return st;
 }
 
 extern "C" {
 
 apd_seg_ctx *apd_seg_create(int32_t device) {
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || device < 0 || device >= n) return nullptr;
-    if (hipSetDevice(device) != hipSuccess) return nullptr;
-    auto *ctx = new apd_seg_ctx();
-    ctx->device = device;
-    bool ok = hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking) == hipSuccess;
+    auto *ctx = open_ctx<apd_seg_ctx>(device);
+    if (!ctx) return nullptr;
+    bool ok = true;
     for (int k = 0; ok && k < NUM_EVENTS; ++k) ok = hipEventCreate(&ctx->ev[k]) == hipSuccess;
     if (!ok) {
         apd_seg_destroy(ctx);
@@ -347,13 +310,10 @@ apd_seg_ctx *apd_seg_create(int32_t device) {
 void apd_seg_destroy(apd_seg_ctx *ctx) {
     if (!ctx) return;
     (void)hipSetDevice(ctx->device);
-    for (Buf *b : {&ctx->src, &ctx->work, &ctx->smooth, &ctx->flat, &ctx->parent, &ctx->roots, &ctx->area, &ctx->keys,
-                   &ctx->keys_sorted, &ctx->labels, &ctx->tmp})
-        if (b->p) (void)hipFree(b->p);
     for (hipEvent_t e : ctx->ev)
         if (e) (void)hipEventDestroy(e);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
-    delete ctx;
+    delete ctx;  // the buffers with it
 }
 
 const char *apd_seg_last_error(const apd_seg_ctx *ctx) {
@@ -364,22 +324,22 @@ int32_t apd_seg_label_mask(apd_seg_ctx *ctx, int32_t W, int32_t H, const uint8_t
     if (!ctx) return APD_EINVAL;
     if (const char *what = check_label_mask(W, H, mask_u8, roots_i32))
         return fail(ctx, std::string("apd_seg_label_mask: ") + what);
-    SG_OK(ctx, hipSetDevice(ctx->device));
+    HIP_OK(ctx, hipSetDevice(ctx->device));
     ctx->last = 0;
     const size_t N = (size_t)W * (size_t)H;
     int st;
     if ((st = grow(ctx, ctx->flat, N))) return st;
     hipStream_t s = ctx->stream;
-    SG_OK(ctx, hipEventRecord(ctx->ev[0], s));
-    SG_OK(ctx, hipMemcpyAsync(ctx->flat.p, mask_u8, N, hipMemcpyDefault, s));
-    SG_OK(ctx, hipEventRecord(ctx->ev[1], s));
-    SG_OK(ctx, hipEventRecord(ctx->ev[2], s));
+    HIP_OK(ctx, hipEventRecord(ctx->ev[0], s));
+    HIP_OK(ctx, hipMemcpyAsync(ctx->flat.p, mask_u8, N, hipMemcpyDefault, s));
+    HIP_OK(ctx, hipEventRecord(ctx->ev[1], s));
+    HIP_OK(ctx, hipEventRecord(ctx->ev[2], s));
     if ((st = run_components(ctx, W, H))) return st;
-    SG_OK(ctx, hipEventRecord(ctx->ev[7], s));
-    SG_OK(ctx, hipEventRecord(ctx->ev[8], s));
-    SG_OK(ctx, hipMemcpyAsync(roots_i32, ctx->roots.p, N * 4, hipMemcpyDefault, s));
-    SG_OK(ctx, hipEventRecord(ctx->ev[9], s));
-    SG_OK(ctx, hipStreamSynchronize(s));
+    HIP_OK(ctx, hipEventRecord(ctx->ev[7], s));
+    HIP_OK(ctx, hipEventRecord(ctx->ev[8], s));
+    HIP_OK(ctx, hipMemcpyAsync(roots_i32, ctx->roots.p, N * 4, hipMemcpyDefault, s));
+    HIP_OK(ctx, hipEventRecord(ctx->ev[9], s));
+    HIP_OK(ctx, hipStreamSynchronize(s));
     if ((st = read_times(ctx))) return st;
     ctx->W = W;
     ctx->H = H;
@@ -393,7 +353,7 @@ int32_t apd_seg_flat_zones_bgr8(apd_seg_ctx *ctx, int32_t w, int32_t h, const ui
     if (!ctx) return APD_EINVAL;
     if (const char *what = check_flat_zones(w, h, src, max_size, threshold_q8, min_area, labels, out_w, out_h))
         return fail(ctx, std::string("apd_seg_flat_zones_bgr8: ") + what);
-    SG_OK(ctx, hipSetDevice(ctx->device));
+    HIP_OK(ctx, hipSetDevice(ctx->device));
     ctx->last = 0;
     const int f = scale_of(w, h, max_size);
     const int W = ceil_div(w, f), H = ceil_div(h, f);
@@ -402,31 +362,31 @@ int32_t apd_seg_flat_zones_bgr8(apd_seg_ctx *ctx, int32_t w, int32_t h, const ui
     if ((st = grow(ctx, ctx->work, 3 * N)) || (st = grow(ctx, ctx->flat, N)) || (st = grow(ctx, ctx->labels, N))) return st;
     if (f > 1 && (st = grow(ctx, ctx->src, src_bytes))) return st;
     hipStream_t s = ctx->stream;
-    SG_OK(ctx, hipEventRecord(ctx->ev[0], s));
-    SG_OK(ctx, hipMemcpyAsync(f > 1 ? ctx->src.p : ctx->work.p, src, src_bytes, hipMemcpyDefault, s));
-    SG_OK(ctx, hipEventRecord(ctx->ev[1], s));
+    HIP_OK(ctx, hipEventRecord(ctx->ev[0], s));
+    HIP_OK(ctx, hipMemcpyAsync(f > 1 ? ctx->src.p : ctx->work.p, src, src_bytes, hipMemcpyDefault, s));
+    HIP_OK(ctx, hipEventRecord(ctx->ev[1], s));
     if (f > 1) {
         hipLaunchKernelGGL(k_seg_downscale, dim3(blocks_for((int64_t)N)), dim3(BLOCK), 0, s, (const uint8_t *)ctx->src.p, w,
                            h, f, (uint8_t *)ctx->work.p, W, H);
-        SG_OK(ctx, hipGetLastError());
+        HIP_OK(ctx, hipGetLastError());
     }
-    SG_OK(ctx, hipEventRecord(ctx->ev[2], s));
+    HIP_OK(ctx, hipEventRecord(ctx->ev[2], s));
     const dim3 tiles((unsigned)ceil_div(W, TW), (unsigned)ceil_div(H, TH));
     hipLaunchKernelGGL(k_seg_smooth_flat<false>, tiles, dim3(BLOCK), 0, s, (const uint8_t *)ctx->work.p, W, H,
                        threshold_q8, (uint8_t *)ctx->flat.p, (uint16_t *)nullptr);
-    SG_OK(ctx, hipGetLastError());
+    HIP_OK(ctx, hipGetLastError());
     if ((st = run_components(ctx, W, H))) return st;
 
     // ranking: the survivors' keys in root order, sorted; the parents are dead and hold the scan
     int *rank_incl = (int *)ctx->parent.p;
     const auto flags = rocprim::make_transform_iterator((const int *)ctx->area.p, IsSurvivor{min_area});
     size_t tb = 0;
-    SG_OK(ctx, rocprim::inclusive_scan(nullptr, tb, flags, rank_incl, N, rocprim::plus<int>(), s));
+    HIP_OK(ctx, rocprim::inclusive_scan(nullptr, tb, flags, rank_incl, N, rocprim::plus<int>(), s));
     if ((st = grow(ctx, ctx->tmp, tb))) return st;
-    SG_OK(ctx, rocprim::inclusive_scan(ctx->tmp.p, tb, flags, rank_incl, N, rocprim::plus<int>(), s));
+    HIP_OK(ctx, rocprim::inclusive_scan(ctx->tmp.p, tb, flags, rank_incl, N, rocprim::plus<int>(), s));
     int survivors = 0;
-    SG_OK(ctx, hipMemcpyAsync(&survivors, rank_incl + (N - 1), sizeof(int), hipMemcpyDeviceToHost, s));
-    SG_OK(ctx, hipStreamSynchronize(s));
+    HIP_OK(ctx, hipMemcpyAsync(&survivors, rank_incl + (N - 1), sizeof(int), hipMemcpyDeviceToHost, s));
+    HIP_OK(ctx, hipStreamSynchronize(s));
     const int top = survivors < APD_SEG_MAX_LABELS ? survivors : APD_SEG_MAX_LABELS;
     uint64_t ranked[APD_SEG_MAX_LABELS];
     if (survivors > 0) {
@@ -434,26 +394,26 @@ int32_t apd_seg_flat_zones_bgr8(apd_seg_ctx *ctx, int32_t w, int32_t h, const ui
         if ((st = grow(ctx, ctx->keys, key_bytes)) || (st = grow(ctx, ctx->keys_sorted, key_bytes))) return st;
         hipLaunchKernelGGL(k_seg_compact, dim3(blocks_for((int64_t)N)), dim3(BLOCK), 0, s, (const int *)ctx->area.p,
                            (const int *)rank_incl, min_area, (int64_t)N, (uint64_t *)ctx->keys.p);
-        SG_OK(ctx, hipGetLastError());
+        HIP_OK(ctx, hipGetLastError());
         tb = 0;
-        SG_OK(ctx, rocprim::radix_sort_keys(nullptr, tb, (const uint64_t *)ctx->keys.p, (uint64_t *)ctx->keys_sorted.p,
+        HIP_OK(ctx, rocprim::radix_sort_keys(nullptr, tb, (const uint64_t *)ctx->keys.p, (uint64_t *)ctx->keys_sorted.p,
                                             (size_t)survivors, 0, 64, s));
         if ((st = grow(ctx, ctx->tmp, tb))) return st;
-        SG_OK(ctx, rocprim::radix_sort_keys(ctx->tmp.p, tb, (const uint64_t *)ctx->keys.p, (uint64_t *)ctx->keys_sorted.p,
+        HIP_OK(ctx, rocprim::radix_sort_keys(ctx->tmp.p, tb, (const uint64_t *)ctx->keys.p, (uint64_t *)ctx->keys_sorted.p,
                                             (size_t)survivors, 0, 64, s));
-        SG_OK(ctx, hipMemcpyAsync(ranked, ctx->keys_sorted.p, (size_t)top * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-        SG_OK(ctx, hipStreamSynchronize(s));
+        HIP_OK(ctx, hipMemcpyAsync(ranked, ctx->keys_sorted.p, (size_t)top * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+        HIP_OK(ctx, hipStreamSynchronize(s));
     }
     LabelTable table;
     table_from_ranked(ranked, top, table);
-    SG_OK(ctx, hipEventRecord(ctx->ev[7], s));
+    HIP_OK(ctx, hipEventRecord(ctx->ev[7], s));
     hipLaunchKernelGGL(k_seg_relabel, dim3(blocks_for((int64_t)N)), dim3(BLOCK), 0, s, (const int *)ctx->roots.p, (int64_t)N,
                        table, (uint8_t *)ctx->labels.p);
-    SG_OK(ctx, hipGetLastError());
-    SG_OK(ctx, hipEventRecord(ctx->ev[8], s));
-    SG_OK(ctx, hipMemcpyAsync(labels, ctx->labels.p, N, hipMemcpyDefault, s));
-    SG_OK(ctx, hipEventRecord(ctx->ev[9], s));
-    SG_OK(ctx, hipStreamSynchronize(s));
+    HIP_OK(ctx, hipGetLastError());
+    HIP_OK(ctx, hipEventRecord(ctx->ev[8], s));
+    HIP_OK(ctx, hipMemcpyAsync(labels, ctx->labels.p, N, hipMemcpyDefault, s));
+    HIP_OK(ctx, hipEventRecord(ctx->ev[9], s));
+    HIP_OK(ctx, hipStreamSynchronize(s));
     if ((st = read_times(ctx))) return st;
     *out_w = W;
     *out_h = H;
@@ -473,7 +433,7 @@ int32_t apd_seg_get_stage(apd_seg_ctx *ctx, int32_t which, void *out) {
         ctx->err = "apd_seg_get_stage: the last call left no such stage";
         return APD_ESTATE;
     }
-    SG_OK(ctx, hipSetDevice(ctx->device));
+    HIP_OK(ctx, hipSetDevice(ctx->device));
     const int W = ctx->W, H = ctx->H;
     const size_t N = (size_t)W * (size_t)H;
     hipStream_t s = ctx->stream;
@@ -487,7 +447,7 @@ int32_t apd_seg_get_stage(apd_seg_ctx *ctx, int32_t which, void *out) {
             const dim3 tiles((unsigned)ceil_div(W, TW), (unsigned)ceil_div(H, TH));
             hipLaunchKernelGGL(k_seg_smooth_flat<true>, tiles, dim3(BLOCK), 0, s, (const uint8_t *)ctx->work.p, W, H, 0,
                                (uint8_t *)nullptr, (uint16_t *)ctx->smooth.p);
-            SG_OK(ctx, hipGetLastError());
+            HIP_OK(ctx, hipGetLastError());
             from = ctx->smooth.p;
             bytes = 6 * N;
             break;
@@ -496,8 +456,8 @@ int32_t apd_seg_get_stage(apd_seg_ctx *ctx, int32_t which, void *out) {
         case APD_SEG_STAGE_ROOTS: from = ctx->roots.p; bytes = 4 * N; break;
         default: from = ctx->area.p; bytes = 4 * N; break;
     }
-    SG_OK(ctx, hipMemcpyAsync(out, from, bytes, hipMemcpyDefault, s));
-    SG_OK(ctx, hipStreamSynchronize(s));
+    HIP_OK(ctx, hipMemcpyAsync(out, from, bytes, hipMemcpyDefault, s));
+    HIP_OK(ctx, hipStreamSynchronize(s));
     return APD_OK;
 }
 
