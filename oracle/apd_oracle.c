@@ -1874,7 +1874,12 @@ float oracle_ncc_new(const apd_problem *pb, int px, int py, int src, const float
               pixels: planes, costs, sel (in/out), vw (out);
      stage 6  RANSACToGetFitPlane at `iter` (APD.cu:2486-2598) with caller-given anchors (in,
               weak_count x 9 x (x, y), row-major WEAK order): planes, weak (in) -> fit;
-     stage 7  LocalRefine (APD.cu:2346-2432): planes (world normal, depth; in/out), sel, vw (in).
+     stage 7  LocalRefine (APD.cu:2346-2432): planes (world normal, depth; in/out), sel, vw (in);
+     stage 8  one colour (0 black, 1 red) of CheckerboardPropagationWeak +
+              PlaneHypothesisRefinementWeak at `iter` (APD.cu:1442-1615, 1008-1096) over the WEAK
+              pixels (tests/test_oracle_kat_weak.py): planes, costs, sel (in/out), weak (in), anchors
+              (in, as stage 6 takes them), fit (IN for this stage only: a zero normal makes the
+              refinement drop out), vw (out).
    Returns APD_OK or a negative status. */
 int oracle_kat_stage_ex(const apd_problem *pb, int stage, int iter, int colour, uint32_t *sel, float *costs,
                         float *planes, uint8_t *weak, uint8_t *conf, int16_t *nearest, int16_t *anchors,
@@ -1901,8 +1906,9 @@ int oracle_kat_stage_ex(const apd_problem *pb, int stage, int iter, int colour, 
             }
             o->weak_count = wc;
         }
-        if (stage == 6 && anchors && o->weak_count > 0)
+        if ((stage == 6 || stage == 8) && anchors && o->weak_count > 0)
             memcpy(o->anchors, anchors, (size_t)o->weak_count * ANCHOR_NUM * 2 * sizeof(int16_t));
+        if (stage == 8 && fit) memcpy(o->fit, fit, HW * sizeof(f4));
     }
     switch (stage) {
     case 0:
@@ -1941,6 +1947,13 @@ int oracle_kat_stage_ex(const apd_problem *pb, int stage, int iter, int colour, 
         break;
     case 7:
         FOR_ALL(o, k_local_refine(o, px, py));
+        break;
+    case 8:
+        if (colour == 0) {
+            FOR_COLOUR(o, 0, if (RD(o, weak, py * o->W + px) == WEAK) k_sweep_weak(o, px, py, iter));
+        } else {
+            FOR_COLOUR(o, 1, if (RD(o, weak, py * o->W + px) == WEAK) k_sweep_weak(o, px, py, iter));
+        }
         break;
     default:
         st = APD_EINVAL;

@@ -15,6 +15,7 @@ borders: a clamp in y acts on both windows alike, and the texture is constant al
 0..4 and from column W - 1 on, so a tap clamped in x reads the value its partner reads.
 """
 import ctypes as C
+from dataclasses import dataclass
 
 import numpy as np
 
@@ -86,17 +87,60 @@ def graded_source(seed=TEX_SEED, noise_seed=1032, lo_deg=50.0, hi_deg=100.0):
     return np.rint(g * 255.0).astype(np.float32)
 
 
-def camera(b=0.0):
-    K = np.array([[F, 0, W / 2.0], [0, F, H / 2.0], [0, 0, 1.0]])
-    return synth.Camera(K, np.eye(3), np.array([-b, 0.0, 0.0]), DMIN, DMAX)
+@dataclass(frozen=True)
+class Rig:
+    """A rig that is the exact-seed rig to every restatement here, and a general one to the code
+    under test: the world moved rigidly (X' = Rg X + cg, so every camera has R' = R Rg^T and
+    t' = t - R' cg), fy != fx in all views, and the sources' principal point moved by `m` whole
+    pixels in x (Ks != Kr). A source at baseline b then sees depth d at x - (F b / d - m): with the
+    baseline baseline(e, rig) the plane at D0 keeps the effective disparity e, the images stay those
+    of images(), and every float64 answer in terms of effective disparities is the identity rig's."""
+    Rg: tuple
+    cg: tuple
+    fy: float
+    m: int
 
 
-def problem(srcs, baselines=None, **params):
+def _rodrigues(axis, deg):
+    a = np.asarray(axis, np.float64)
+    a = a / np.linalg.norm(a)
+    Kx = np.array([[0, -a[2], a[1]], [a[2], 0, -a[0]], [-a[1], a[0], 0]])
+    th = np.deg2rad(deg)
+    return np.eye(3) + np.sin(th) * Kx + (1 - np.cos(th)) * (Kx @ Kx)
+
+
+# 25 degrees about (1, 2, 3): no zero entry, not symmetric
+MOVED = Rig(tuple(map(tuple, _rodrigues((1.0, 2.0, 3.0), 25.0))), (0.3, -1.1, 2.0), 80.0, 2)
+
+
+def baseline(eff_disparity=SHIFT, rig=None):
+    """The baseline at which the plane at D0 has the given effective disparity."""
+    return D0 * (eff_disparity + (rig.m if rig else 0)) / F
+
+
+def depth_of(eff_disparity, rig=None):
+    """Depth of the fronto-parallel plane with the given effective disparity under baseline(SHIFT, rig)."""
+    m = rig.m if rig else 0
+    return F * baseline(SHIFT, rig) / (np.asarray(eff_disparity, np.float64) + m)
+
+
+def camera(b=0.0, rig=None, source=False):
+    fy = rig.fy if rig else F
+    m = rig.m if rig and source else 0
+    K = np.array([[F, 0, W / 2.0 + m], [0, fy, H / 2.0], [0, 0, 1.0]])
+    R, t = np.eye(3), np.array([-b, 0.0, 0.0])
+    if rig:
+        R = R @ np.asarray(rig.Rg).T
+        t = t - R @ np.asarray(rig.cg)
+    return synth.Camera(K, R, t, DMIN, DMAX)
+
+
+def problem(srcs, baselines=None, rig=None, **params):
     """ProblemArrays with the reference image of images() and the given source images; baselines
-    default to B for every source."""
+    default to baseline(SHIFT, rig) (B on the identity rig) for every source."""
     ref, _ = images()
-    baselines = baselines or [B] * len(srcs)
-    cams = [camera(0.0)] + [camera(b) for b in baselines]
+    baselines = baselines or [baseline(SHIFT, rig)] * len(srcs)
+    cams = [camera(0.0, rig)] + [camera(b, rig, source=True) for b in baselines]
     vals = [synth.camera_struct_values(c, W, H) for c in cams]
     p = A.default_params(1 + len(srcs), DMIN, DMAX)
     for k, v in params.items():
@@ -104,14 +148,22 @@ def problem(srcs, baselines=None, **params):
     return A.ProblemArrays(W, H, [ref] + list(srcs), vals, p)
 
 
-def plane_field(disparity):
-    """H x W x 4 fronto-parallel planes at the given disparity (scalar or H x W): normal (0, 0, -1);
-    w is the distance to the origin in the sweep's form (= the depth, APD.cu:218-223) and the depth in
-    the input form (world normal, depth) alike."""
-    d = np.broadcast_to(np.asarray(F * B / np.asarray(disparity, np.float64), np.float32), (H, W))
+def plane_field(disparity, rig=None):
+    """H x W x 4 fronto-parallel planes at the given (effective) disparity (scalar or H x W): normal
+    (0, 0, -1); w is the distance to the origin in the sweep's form (= the depth, APD.cu:218-223) and,
+    on the identity rig, the depth in the input form (world normal, depth) alike."""
+    d = np.broadcast_to(np.asarray(depth_of(disparity, rig), np.float32), (H, W))
     pl = np.zeros((H, W, 4), np.float32)
     pl[..., 2] = -1.0
     pl[..., 3] = d
+    return pl
+
+
+def input_plane_field(disparity, rig=None):
+    """The same field in the input form: (world normal, depth), world normal = Rg n_ref."""
+    pl = plane_field(disparity, rig)
+    if rig:
+        pl[..., :3] = (np.asarray(rig.Rg) @ np.array([0.0, 0.0, -1.0])).astype(np.float32)
     return pl
 
 
@@ -410,9 +462,9 @@ def geom_cost(px, py, depth, src_depth_map, b=B, dtype=np.float64, pick=int):
 # ------------------------------------------------------------------------------------------------
 # problems shared by the CPU known-answer tests and their runs on the HIP engine
 # ------------------------------------------------------------------------------------------------
-def seeded_field(disparity, seeds=SEEDS):
+def seeded_field(disparity, seeds=SEEDS, rig=None, input_form=False):
     """(planes, exact mask): the fronto-parallel field at `disparity` with the exact plane at seeds."""
-    pl = plane_field(disparity)
+    pl = (input_plane_field if input_form else plane_field)(disparity, rig)
     exact = np.zeros((H, W), bool)
     for (x, y) in seeds:
         pl[y, x, 3] = np.float32(D0)
@@ -420,11 +472,11 @@ def seeded_field(disparity, seeds=SEEDS):
     return pl, exact
 
 
-def footprint_problem(disparity, state):
+def footprint_problem(disparity, state, rig=None):
     """One exact-shift source; the prior is the field at `disparity` with the SEEDS exact."""
     _, src = images()
-    arr = problem([src], state=state)
-    arr.init_planes, exact = seeded_field(disparity)
+    arr = problem([src], rig=rig, state=state)
+    arr.init_planes, exact = seeded_field(disparity, rig=rig, input_form=True)
     return arr, exact
 
 
@@ -435,7 +487,7 @@ def field_costs(disparity=None):
     return c_exact, (ncc_shift(ref, src, float(disparity)) if disparity is not None else None)
 
 
-def init_problem(top_k, kinds=("exact", "exact", "near", "flat")):
+def init_problem(top_k, kinds=("exact", "exact", "near", "flat"), rig=None):
     """RandomInitialization's problem: sources that see the d0 plane at cost 0 (exact shift), at the
     near-miss cost (the same image from a baseline that makes d0's disparity 4.5) or not at all (a
     constant image: variance floor, cost 2). Returns (problem, H x W x N float64 expected view costs)."""
@@ -444,8 +496,8 @@ def init_problem(top_k, kinds=("exact", "exact", "near", "flat")):
     srcs, bl, cv = [], [], []
     for k in kinds:
         srcs.append(np.full((H, W), 90.0, np.float32) if k == "flat" else src)
-        bl.append(B * NEAR_DISP / SHIFT if k == "near" else B)
+        bl.append(baseline(NEAR_DISP if k == "near" else SHIFT, rig))
         cv.append({"exact": c_exact, "near": c_near, "flat": np.full((H, W), 2.0)}[k])
-    arr = problem(srcs, bl, state=A.REFINE_ITER, top_k=top_k)
-    arr.init_planes = plane_field(float(SHIFT))
+    arr = problem(srcs, bl, rig=rig, state=A.REFINE_ITER, top_k=top_k)
+    arr.init_planes = input_plane_field(float(SHIFT), rig)
     return arr, np.stack(cv, -1)

@@ -4,10 +4,12 @@ For each mutation below -- one reference rule or quirk restated wrongly -- build
 oracle/apd_oracle.c into a temporary liboracle.so and run the known-answer tests against it
 (APD_ORACLE_SO): the APD half's (MUTATIONS) against tests/test_oracle_kat_apd.py and
 tests/test_oracle_kat.py, the Strong half's (STRONG_MUTATIONS) against
-tests/test_oracle_kat_strong.py. FUSION_MUTATIONS mutate oracle/fusion_oracle.c instead and run
+tests/test_oracle_kat_strong.py, the Weak sweep's and the moved-rig geometry's (WEAK_MUTATIONS,
+GEOMETRY_MUTATIONS) against tests/test_oracle_kat_weak.py. FUSION_MUTATIONS mutate oracle/fusion_oracle.c instead and run
 tests/test_oracle_kat_fusion.py plus the oracle tests of tests/test_fusion.py. A mutation the tests
 do not reject ("survived") marks a rule the KATs do not pin. Usage: python tools/mutate_oracle.py
-[--json apd.json] [--strong-json strong.json] [--fusion-json fusion.json] [--only apd|strong|fusion]
+[--json apd.json] [--strong-json strong.json] [--weak-json weak.json] [--fusion-json fusion.json]
+[--only apd|strong|weak|fusion]
 [--jobs N]
 """
 import concurrent.futures
@@ -239,8 +241,128 @@ FUSION_MUTATIONS = [
      "int ref_index = index_of(n, v, v[i].ref_id);", "int ref_index = i;"),
 ]
 
+# the Weak sweep: every text below is one line of k_sweep_weak (or, for rule d, of the view_selection
+# it shares with the Strong sweep, or of the launch set-up), run against tests/test_oracle_kat_weak.py
+_W_ADOPT = ("if (db >= o->P.depth_min && db <= o->P.depth_max && fc[mi] < cost_now) {\n"
+            "            depth_now = db; pnow = newp[mi]; cost_now = fc[mi];")
+_W_ARGMIN = ("{ float m = fc[0]; for (int j = 1; j < 8; ++j) if (fc[j] <= m) { m = fc[j]; mi = j; } }\n"
+             "    f4 cur = RD(o, plane, c);\n    float cost_now = 0.0f;\n    for (int i = 0; i < N; ++i) {\n"
+             "        float v = o_ncc_new(")
+_W_INIT = ("if ((double)cost_now < (double)cost_init - 0.1) { WR(o, cost, c) = cost_now; WR(o, plane, c) = pnow; }\n"
+           "        else WR(o, cost, c) = cost_init;\n    } else {\n        WR(o, cost, c) = cost_now; WR(o, plane, c) = pnow;\n"
+           "    }\n    for (int i = 0; i < N; ++i) WR(o, vw, (size_t)i * o->HW + c) = vw[i];\n}\n\n/* PointinTriangle")
+_W_FIT = "if (db >= o->P.depth_min && db <= o->P.depth_max && tc < cost_now) { depth_now = db; pnow = fit; cost_now = tc; }"
+_W_GEOM = "flag[j] ? fmaf(gf, o_geom_cost(o, px, py, i + 1, RD(o, plane, pos[j])), v) : fmaf(gf, 3.0f, v);"
+
+WEAK_MUTATIONS = [
+    ("a: an anchor need not be STRONG to be a candidate", "APD.cu:1473",
+     "if (ax == -1 || ay == -1 || RD(o, weak, ax + ay * W) != STRONG) continue;", "if (ax == -1 || ay == -1) continue;"),
+    ("a: the candidate's plane is read at the WEAK pixel", "APD.cu:1481",
+     "newp[i] = RD(o, plane, pos[i]);", "newp[i] = RD(o, plane, c);"),
+    ("b: flagless rows hold 2.0 instead of 0", "APD.cu:1464",
+     "memset(ca, 0, sizeof(ca));\n    ca[0][0] = 2.0f;\n    int flag[8] = {0}, pos[8] = {0};",
+     "for (int j = 0; j < 8; ++j) for (int i = 0; i < 32; ++i) ca[j][i] = 2.0f;\n    int flag[8] = {0}, pos[8] = {0};"),
+    ("b: cost_array[0][0] left at 0", "APD.cu:1464",
+     "ca[0][0] = 2.0f;\n    int flag[8] = {0}, pos[8] = {0};", "ca[0][0] = 0.0f;\n    int flag[8] = {0}, pos[8] = {0};"),
+    ("b: FindMinCostIndex <= -> < (Weak sweep)", "APD.cu:65,1575", _W_ARGMIN, _W_ARGMIN.replace("fc[j] <= m", "fc[j] < m")),
+    ("b: flagless rows left out of the argmin", "APD.cu:1575,1594",
+     _W_ARGMIN, _W_ARGMIN.replace("if (fc[j] <= m)", "if (flag[j] && fc[j] <= m)")),
+    ("c: priors summed over candidates only", "APD.cu:1492",
+     "if (ax == -1 || ay == -1) continue;\n        for (int j = 0; j < N; ++j) prior[j] +=",
+     "if (ax == -1 || ay == -1 || RD(o, weak, ax + ay * W) != STRONG) continue;\n        for (int j = 0; j < N; ++j) prior[j] +="),
+    ("c: priors 0.9 / 0.1 swapped (Weak sweep)", "APD.cu:1496-1501",
+     "prior[j] += is_set(RD(o, sel, ax + ay * W), j) ? 0.9f : 0.1f;", "prior[j] += is_set(RD(o, sel, ax + ay * W), j) ? 0.1f : 0.9f;"),
+    ("d: threshold 0.8 -> 0.9", "APD.cu:1506",
+     "(float)(0.8 * (double)o_expf(FDIV((float)(iter * iter), (-90.0f))))",
+     "(float)(0.9 * (double)o_expf(FDIV((float)(iter * iter), (-90.0f))))"),
+    ("d: threshold ignores iter", "APD.cu:1506",
+     "(float)(0.8 * (double)o_expf(FDIV((float)(iter * iter), (-90.0f))))", "0.8f"),
+    ("d: count > 2 -> count > 3", "APD.cu:1520",
+     "if (count > 2 && cf < 3) p = FDIV(tmpw, count);", "if (count > 3 && cf < 3) p = FDIV(tmpw, count);"),
+    ("d: above 1.2 -> above 1.0", "APD.cu:1516", "if (c > 1.2f) cf++;", "if (c > 1.0f) cf++;"),
+    ("d: fewer than 3 above 1.2 -> fewer than 4", "APD.cu:1520-1523",
+     "if (count > 2 && cf < 3) p = FDIV(tmpw, count);\n        else if (cf < 3)",
+     "if (count > 2 && cf < 4) p = FDIV(tmpw, count);\n        else if (cf < 4)"),
+    ("d: fallback exp(-thr^2 / 0.32) -> 0.18", "APD.cu:1524",
+     "p = o_expf(FDIV(thr * thr, (-0.32f)));", "p = o_expf(FDIV(thr * thr, (-0.18f)));"),
+    ("d: 16 draws instead of 15", "APD.cu:1530", "for (int smp = 0; smp < 15; ++smp) {", "for (int smp = 0; smp < 16; ++smp) {"),
+    ("e: no view drawn leaves cost 0, not NaN", "APD.cu:1589",
+     "cost_now /= wn;\n    const float cost_init = cost_now;\n    float depth_now = depth_from_plane(cam, cur, px, py);\n"
+     "    f4 pnow = cur;\n    if (flag[mi]) {\n        float db = depth_from_plane(cam, newp[mi]",
+     "if (wn > 0) cost_now /= wn;\n    const float cost_init = cost_now;\n    float depth_now = depth_from_plane(cam, cur, px, py);\n"
+     "    f4 pnow = cur;\n    if (flag[mi]) {\n        float db = depth_from_plane(cam, newp[mi]"),
+    ("g: adoption < -> <=", "APD.cu:1596", _W_ADOPT, _W_ADOPT.replace("fc[mi] < cost_now", "fc[mi] <= cost_now")),
+    ("g: adoption ignores the depth range", "APD.cu:1596", _W_ADOPT,
+     _W_ADOPT.replace("db >= o->P.depth_min && db <= o->P.depth_max && ", "")),
+    ("g: depth range without its ends", "APD.cu:1596", _W_ADOPT,
+     _W_ADOPT.replace("db >= o->P.depth_min && db <= o->P.depth_max", "db > o->P.depth_min && db < o->P.depth_max")),
+    ("g: selected_views written without adoption", "APD.cu:1600",
+     "if (flag[mi]) {\n        float db = depth_from_plane(cam, newp[mi], px, py);",
+     "WR(o, sel, c) = tsel;\n    if (flag[mi]) {\n        float db = depth_from_plane(cam, newp[mi], px, py);"),
+    ("g: selected_views takes every view, not the weight mask", "APD.cu:1600",
+     "cost_now = fc[mi];\n            WR(o, sel, c) = tsel;\n        }\n    }\n    /* PlaneHypothesisRefinementWeak",
+     "cost_now = fc[mi];\n            WR(o, sel, c) = (1u << N) - 1u;\n        }\n    }\n    /* PlaneHypothesisRefinementWeak"),
+    ("h: refinement not skipped for a zero fit normal", "APD.cu:1028-1030",
+     "if (!(fit.x == 0 && fit.y == 0 && fit.z == 0)) {", "if (1) {"),
+    ("h: the fit plane is not tried", "APD.cu:1046-1051", _W_FIT, "(void)db;"),
+    ("h: the fit plane ignores the depth range", "APD.cu:1047", _W_FIT,
+     _W_FIT.replace("db >= o->P.depth_min && db <= o->P.depth_max && ", "")),
+    ("h: candidates built from the plane before the fit step", "APD.cu:1055-1067",
+     "refine_candidates(o, px, py, &g, pnow, depth_now, dc, nc);\n#ifdef ORACLE_WEAK_STATS\n        const float thr5",
+     "refine_candidates(o, px, py, &g, cur, depth_from_plane(cam, cur, px, py), dc, nc);\n#ifdef ORACLE_WEAK_STATS\n        const float thr5"),
+    ("i: REFINE_INIT: cost - 0.1 -> cost (Weak sweep)", "APD.cu:1606", _W_INIT, _W_INIT.replace("cost_init - 0.1", "cost_init")),
+    ("i: REFINE_INIT compares with the cost of before the launch", "APD.cu:1590,1606",
+     _W_INIT, _W_INIT.replace("(double)cost_init - 0.1", "(double)RD(o, cost, c) - 0.1")),
+    ("j: flagless rows add no geometric term", "APD.cu:1564", _W_GEOM, _W_GEOM.replace(": fmaf(gf, 3.0f, v);", ": v;")),
+    ("j: flagless rows add geom_factor * 2", "APD.cu:1564", _W_GEOM, _W_GEOM.replace("3.0f", "2.0f")),
+    ("j: candidate rows add no geometric term", "APD.cu:1561", _W_GEOM,
+     "flag[j] ? v : fmaf(gf, 3.0f, v);"),
+    ("j: cost_now without its geometric term (Weak sweep)", "APD.cu:1583",
+     "float v = o_ncc_new(o, px, py, i + 1, cur);\n        if (geom) v = fmaf(gf, o_geom_cost(o, px, py, i + 1, cur), v);",
+     "float v = o_ncc_new(o, px, py, i + 1, cur);"),
+    ("k: the red Weak launch is left out", "APD.cu:1636-1652",
+     "        FOR_COLOUR(o, 1, if (RD(o, weak, py * o->W + px) == WEAK) k_sweep_weak(o, px, py, it));\n    }\n}", "    }\n}"),
+    ("k: launches stop at half the rows", "APD.cu:1617-1634", "int rl = 32 * ((hh + 15) / 16);", "int rl = 16 * ((hh + 15) / 16);"),
+]
+
+# geometry away from the identity, against the moved-rig tests of tests/test_oracle_kat_weak.py
+_TO_WORLD = ("f4 r = {c->R[0] * p.x + c->R[3] * p.y + c->R[6] * p.z, c->R[1] * p.x + c->R[4] * p.y + c->R[7] * p.z,\n"
+             "            c->R[2] * p.x + c->R[5] * p.y + c->R[8] * p.z, p.w};")
+_TO_REF = ("f4 r = {c->R[0] * p.x + c->R[1] * p.y + c->R[2] * p.z, c->R[3] * p.x + c->R[4] * p.y + c->R[5] * p.z,\n"
+           "            c->R[6] * p.x + c->R[7] * p.y + c->R[8] * p.z, p.w};")
+_RREL = ("(double)c->R[3 * i] * r->R[3 * j] + (double)c->R[3 * i + 1] * r->R[3 * j + 1] +\n"
+         "                                  (double)c->R[3 * i + 2] * r->R[3 * j + 2];")
+_WP = ("float t0 = c->R[0] * X0 + c->R[3] * X1 + c->R[6] * X2;\n    float t1 = c->R[1] * X0 + c->R[4] * X1 + c->R[7] * X2;\n"
+       "    float t2 = c->R[2] * X0 + c->R[5] * X1 + c->R[8] * X2;")
+_PC = ("float t0 = c->R[0] * P[0] + c->R[1] * P[1] + c->R[2] * P[2] + c->t[0];\n"
+       "    float t1 = c->R[3] * P[0] + c->R[4] * P[1] + c->R[5] * P[2] + c->t[1];\n"
+       "    float t2 = c->R[6] * P[0] + c->R[7] * P[1] + c->R[8] * P[2] + c->t[2];")
+
+GEOMETRY_MUTATIONS = [
+    ("to_ref transposed", "APD.cu:415-423", _TO_REF, _TO_WORLD),
+    ("to_world transposed", "APD.cu:405-413", _TO_WORLD, _TO_REF),
+    ("R_relative with the factors swapped", "APD.cu:350-360", _RREL,
+     _RREL.replace("c->R", "@").replace("r->R", "c->R").replace("@", "r->R")),
+    ("reference centre from R instead of R^T", "APD.cu:362-370",
+     "rC[j] = -((double)r->R[j] * r->t[0] + (double)r->R[3 + j] * r->t[1] + (double)r->R[6 + j] * r->t[2]);",
+     "rC[j] = -((double)r->R[3 * j] * r->t[0] + (double)r->R[3 * j + 1] * r->t[1] + (double)r->R[3 * j + 2] * r->t[2]);"),
+    ("depth_from_plane: K[0] and K[4] exchanged", "APD.cu:237-240",
+     "return FDIV(-pl.w * c->K[0],\n                (((float)px - c->K[2]) * pl.x + FDIV(c->K[0], c->K[4]) * ((float)py - c->K[5]) * pl.y + c->K[0] * pl.z));",
+     "return FDIV(-pl.w * c->K[4],\n                (((float)px - c->K[2]) * pl.x + FDIV(c->K[4], c->K[0]) * ((float)py - c->K[5]) * pl.y + c->K[4] * pl.z));"),
+    ("precompute_homography: Kr in the place of Ks", "APD.cu:334-346",
+     "double Ks[9] = {c->K[0], 0.0, c->K[2], 0.0, c->K[4], c->K[5], 0.0, 0.0, c->K[8]};",
+     "double Ks[9] = {r->K[0], 0.0, r->K[2], 0.0, r->K[4], r->K[5], 0.0, 0.0, r->K[8]};"),
+    ("precompute_homography: Ks in the place of Kr", "APD.cu:334-346",
+     "double kr0 = r->K[0], kr2 = r->K[2], kr4 = r->K[4], kr5 = r->K[5];",
+     "const apd_camera *q = &o->cam[1];\n    double kr0 = q->K[0], kr2 = q->K[2], kr4 = q->K[4], kr5 = q->K[5];"),
+    ("Get3DPointonWorld_cu: R instead of R^T", "APD.cu:841-843", _WP, _transpose(_WP)),
+    ("ProjectonCamera_cu: R^T instead of R", "APD.cu:856-858", _PC, _transpose(_PC)),
+    ("get3d: y over fx", "APD.cu:197-202", "X[1] = FDIV(depth * (py - c->K[5]), c->K[4]);", "X[1] = FDIV(depth * (py - c->K[5]), c->K[0]);"),
+]
+
 TESTS = ["tests/test_oracle_kat_apd.py", "tests/test_oracle_kat.py"]
 STRONG_TESTS = ["tests/test_oracle_kat_strong.py"]
+WEAK_TESTS = ["tests/test_oracle_kat_weak.py"]
 FUSION_TESTS = ["tests/test_oracle_kat_fusion.py", "tests/test_fusion.py::test_oracle_runfusion_known_answer",
                 "tests/test_fusion.py::test_oracle_tat_known_answer",
                 "tests/test_fusion.py::test_oracle_weak_filter_only_flags_weak"]
@@ -290,6 +412,7 @@ def main():
     for half, flag, mutations, tests, target in (
             ("apd", "--json", MUTATIONS, TESTS, "apd_oracle.c"),
             ("strong", "--strong-json", STRONG_MUTATIONS, STRONG_TESTS, "apd_oracle.c"),
+            ("weak", "--weak-json", WEAK_MUTATIONS + GEOMETRY_MUTATIONS, WEAK_TESTS, "apd_oracle.c"),
             ("fusion", "--fusion-json", FUSION_MUTATIONS, FUSION_TESTS, "fusion_oracle.c")):
         if only not in (None, half):
             continue
